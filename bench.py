@@ -12,18 +12,33 @@ resident in HBM; chunks are independent, so ranks share nothing and no collectiv
 max-over-ranks step time; `config.rank_bytes` lists every rank's byte range of the stream.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg4|cfg5|cfg2]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
-Prints ONE JSON line on rank 0.  `roofline` prices the merge-scan kernel alone (HIP events on
-its stream around each launch) against HBM: algorithmic bytes = input bytes + 2 x output
-tokens; `traffic` is the PMC-measured HBM bytes per launch from profiles/traffic.json, used only
-when that record names this workload, size and the sha256 of the kernel source it was measured
-on (else null).  `cpu_baseline` times the C restatement of the reference (hash-map, multi-pass,
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the
+line: `value`, `ms_per_step` and `roofline`, which prices the merge-scan kernel alone (HIP events
+on its stream around each launch of the timed steps) against HBM: algorithmic bytes = input bytes
++ 2 x output tokens; `traffic` is the PMC-measured HBM bytes per launch from profiles/traffic.json,
+used only when that record names this workload, size and the sha256 of the kernel source it was
+measured on (else null).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step left in the caller's
+device buffers (the inputs are seeded: the same arguments give the same inputs in every run):
+  DIR/chunk_offsets.npy  float64, the chunks' token offsets (chunks + 1 values, the last one the
+                         token count): all of them;
+  DIR/tokens.npy         float32, the u16 tokens of the output stream: all of them up to
+                         DUMP_TOKENS, else the tokens at DUMP_TOKENS seeded positions (sorted);
+  DIR/token_index.npy    float64, the position in the stream of each token of tokens.npy.
+At N > 1 every rank writes its shard's arrays as <name>.rank<r>.npy.
+
+--full adds everything below (off by default; the figures above are measured the same way with or
+without it).  `cpu_baseline` times the C restatement of the reference (hash-map, multi-pass,
 task-per-chunk) on rank 0's shard (N = 1 only) with one thread per usable host core (num_cpus
 semantics: min(cgroup quota, affinity mask)); its output doubles as the bit-exact check of the
-GPU output; `cpu_baseline_optimized` times a dense-table single-pass CPU version beside it.
+GPU output (`bit_exact_vs_oracle`; at N > 1 every rank checks its own shard);
+`cpu_baseline_optimized` times a dense-table single-pass CPU version beside it.
 
-At N = 1 with the cfg3 workload the line also carries (rank 0, outside the timed region):
+With --full at N = 1 with the cfg3 workload the line also carries (rank 0, outside the timed region):
   * `configs`: the other workloads device-resident, kernel-only (median of HIP-event timings),
     each with its roofline fraction and a bit-exact check: cfg2, cfg5 (the whole 4 GiB stream on
     one GPU), and the general maps of row f2 (the whole encode_device call: byte pass, u16 passes,
@@ -61,9 +76,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bytes-per-gpu", type=int, default=GIB, help="cfg3's bytes per rank")
     ap.add_argument("--total-bytes", type=int, default=0, help="cfg4 / cfg5 stream size (default 8 GiB / 4 GiB)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip configs / end_to_end / per_chunk_path / cli")
-    ap.add_argument("--only-configs", default="", help="comma list: run only these `configs` rows")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines, the bit-exact checks against the oracle and (N = 1, cfg3) "
+                         "configs / end_to_end / per_chunk_path / cli_end_to_end")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip configs / end_to_end / per_chunk_path / cli")
+    ap.add_argument("--only-configs", default="", help="with --full: comma list, run only these `configs` rows")
     ap.add_argument("--events-outside-timed-loop", action="store_true",
                     help="time the kernel's HIP events in a second loop instead of inside the timed region "
                          "(experiment: shows what the event records cost `value`)")
@@ -76,7 +97,12 @@ def parse():
                     help="0: every usable host core (num_cpus semantics)")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes per launch (from tools/pmc_profile.py runs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.only_configs and not args.full:
+        ap.error("--only-configs needs --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def usable_cores():
@@ -427,6 +453,32 @@ def build_merges(synth):
     return synth.merges_dict(synth.text_merges_50k(sample, seed=3))
 
 
+DUMP_TOKENS = 4 << 20   # tokens.npy (float32) 16 MiB + token_index.npy (float64) 32 MiB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, d_out, d_off, rank=0, world=1):
+    """--dump-outputs: the arrays the timed call left in the caller's buffers after the last timed
+    step, as .npy files (under 64 MB in all).  d_out holds the tokens as big-endian u16 pairs,
+    d_off the chunks' token offsets; a stream of more than DUMP_TOKENS tokens is sampled at
+    DUMP_TOKENS positions drawn from a fixed seed and the token count (sorted, so the same build
+    gives the same file)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    off = d_off.cpu().numpy()
+    tokens = int(off[-1])
+    if tokens <= DUMP_TOKENS:
+        idx = np.arange(tokens, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, tokens, DUMP_TOKENS, dtype=np.int64))
+    pos = torch.from_numpy(idx).to(d_out.device)
+    tok = d_out[2 * pos].to(torch.float32) * 256.0 + d_out[2 * pos + 1].to(torch.float32)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, arr in (("chunk_offsets", off.astype(np.float64)), ("tokens", tok.cpu().numpy()),
+                      ("token_index", idx.astype(np.float64))):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
+
+
 def relaunch(n):
     """`python bench.py --gpus N` outside a launcher: start one process per GPU under
     torch.distributed.run as a child (nothing here has touched the GPU) and return its exit code."""
@@ -524,6 +576,8 @@ def main():
         strategy.check_workspace(ws.data_ptr(), sp)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
     tokens = int(d_off[-1].item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, d_off, rank, world)
 
     elapsed, kern_ms_max = shard.max_over_ranks([elapsed, kern_ms], device="cuda" if backend == "nccl" else None)
     ranges = shard.gather_ranges((b0, b1), device="cuda" if backend == "nccl" else None)
@@ -542,7 +596,9 @@ def main():
     usable, affinity, ncpu = usable_cores()
     threads = max(1, args.cpu_threads or usable)
     extras = {}
-    if distributed and not args.no_cpu_baseline:
+    if not args.full:
+        pass   # a plain run: the timed steps' figures only
+    elif distributed and not args.no_cpu_baseline:
         # N > 1: the CPU baseline is reported at N = 1 only; EVERY rank checks its own shard
         # bit-exact against the C oracle (outside the timed region, the host cores split between
         # the ranks), and the flags are ANDed over the ranks (an all_reduce MIN of 0/1)
@@ -577,7 +633,7 @@ def main():
                                  f"pass per chunk (single-pass map), {threads} threads", "seconds": round(fast_s, 3),
                        "matches_port": bool(np.array_equal(fast, exp))}
         del fast
-    if rank == 0 and not distributed and not args.no_extra and wl == "cfg3":
+    if args.full and rank == 0 and not distributed and not args.no_extra and wl == "cfg3":
         # the other configs (kernel-only rates) and the host paths; --only-configs runs a subset, also
         # without the CPU baseline (every row still checks its output against the oracle)
         from oracle import oracle as O

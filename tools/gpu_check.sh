@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -3 "$O/gpu_tests.log"
 timeout -k 10 120 python -c 'import __graft_entry__ as g; g.smoke()' > "$O/smoke.log" 2>&1
 tail -1 "$O/smoke.log"
-timeout -k 10 400 python bench.py > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 400 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"
 cat "$O/bench.json"
 cd /tmp && export TMPDIR=/tmp
 for w in cfg3 cfg5 cfg2; do

@@ -8,14 +8,14 @@
 # Steps (outputs under gpurun_out/TAG/):
 #   tests              pytest -m gpu (every parity test), tests.log
 #   smoke              __graft_entry__.smoke(), smoke.log
-#   bench              the driver's command: bench.py --gpus 1 --steps 20 --warmup 5, bench.json
-#   bench:ARGS         bench.py with extra arguments (+ for spaces), bench_<n>.json
+#   bench              the whole benchmark: bench.py --gpus 1 --steps 20 --warmup 5 --full, bench.json
+#   bench:ARGS         bench.py with extra arguments (+ for spaces; --full for more than the timed steps), bench_<n>.json
 #   benche:NAME=VALUE:ARGS  bench.py with one environment setting
 #   benchlib:LIBTAG:ARGS  bench.py on build/xp/libblt_bpe_LIBTAG.so
 #   kbench[:LIBTAG]    tools/kbench.py on cfg2/cfg3/cfg5 (LIBTAG: build/xp/libblt_bpe_LIBTAG.so)
 #   tim:LIBTAG[:ARGS]  tools/tile_timing.py on a timing build (build/xp/libblt_bpe_LIBTAG.so)
 #   prof:WL            rocprofv3 --kernel-trace --stats of bench.py --workload WL (cfg2|cfg3|cfg5)
-#   proff2[:ROWS]      rocprofv3 kernel stats of the f2 rows (bench.py --only-configs ROWS)
+#   proff2[:ROWS]      rocprofv3 kernel stats of the f2 rows (bench.py --full --only-configs ROWS)
 #   pmc:WL[:GROUPS]    tools/pmc_profile.py on bench.py --workload WL (groups default fetch,write,insts)
 #   pmc4:G             PMC traffic of cfg4's per-rank shard of G GiB (N = 8/4/2: G = 1/2/4)
 #   pmcf2:ROW[:GROUPS] PMC of one f2 row (tools/f2_row.py: every kernel of its calls, traffic per call)
@@ -46,7 +46,7 @@ for st in "$@"; do
       tail -1 "$O/smoke.log" ;;
     bench)
       if [ -z "$a" ]; then
-        timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err"
+        timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench.json" 2> "$O/bench.err"
         python tools/summarize_bench.py "$O/bench.json"
       else
         nb=$((nb + 1))
@@ -83,7 +83,7 @@ for st in "$@"; do
       rows=${a:-multi,wrap,selfval,chain}
       bt=${b##*/}; pd=prof_f2${a:+_${a//,/_}}${b:+_${bt//[=.]/_}}
       (cd /tmp && export TMPDIR=/tmp && { [ -z "$b" ] || export "$b"; } && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$O/$pd" -o run -- python3 "$R/bench.py" --steps 3 --warmup 1 --only-configs "$rows" \
+        -d "$O/$pd" -o run -- python3 "$R/bench.py" --steps 3 --warmup 1 --full --only-configs "$rows" \
         > "$O/$pd.log" 2>&1)
       find "$O/$pd" -name '*kernel_stats.csv' -exec head -12 {} \; | cut -c1-160 ;;
     pmc)
