@@ -610,6 +610,9 @@ thread_local uint32_t t_last_scan_passes = 0;
 // Test hook: how the calling thread's last synchronous general-map encode ran passes 1 and 2:
 // 0 two kernels, 1 fused, 2 fused and fell back (blt_debug_last_fused).
 thread_local uint32_t t_last_fused = 0;
+// Test hook: the tile (positions) of the byte-pass instantiation the calling thread launched last
+// (blt_debug_last_byte_tile).
+thread_local uint32_t t_last_byte_tile = 0;
 
 // ---- workspace layout -------------------------------------------------------------------
 inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
@@ -739,7 +742,11 @@ int run_pass(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8
              uint64_t out_cap, uint64_t* chunk_off, bool ws_zeroed = false, const Chain* chain = nullptr,
              bool tok_scan = false, U16Run* run = nullptr) {
     const bool columnar = !in_u16 && cs >= blt::kMinChunkBytes && h->byte_mode >= 0 && be;   // byte-pass fast kernel
-    const uint64_t tile = columnar ? blt::kTilePosBytes
+    // the byte pass's tile is the picked instantiation's (48 KiB for merges files, else 32 KiB): this
+    // line gives the launch its ntiles, and the kernel uses the first ntiles of the workspace's
+    // ceil(n / kTilePosBytes) status words (ws_layout, blt_bpe_workspace_reset: 32 KiB units, unchanged)
+    const int byte_live = (chain && h->live_first) ? 1 : 0;
+    const uint64_t tile = columnar ? blt::scan_bytes_tile(h->byte_mode, byte_live)
                                    : in_u16 ? (tok_scan ? blt::kTilePosTok : blt::kTilePosU16) : blt::kTilePos;
     const uint64_t ntiles = (n + tile - 1) / tile;
     if (ntiles > 0xFFFFFFFFull) return fail(BLT_E_INVALID_INPUT, "input too large");
@@ -779,9 +786,11 @@ int run_pass(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8
     p.hbytes = (uint32_t)(h->hwords.size() * sizeof(uint32_t));
     p.hone = h->hone ? 1u : 0u;
     p.cs_magic = cs ? ~0ull / cs : 0;
-    if (cs && cs % blt::kTilePosBytes == 0 && cs / blt::kTilePosBytes < (1ull << 31)) {
-        p.cs_tiles = (uint32_t)(cs / blt::kTilePosBytes);
-        p.cs_tiles_magic = p.cs_tiles > 1 ? (uint32_t)(0xFFFFFFFFull / p.cs_tiles) : 0u;
+    if (cs && cs % blt::kSubPosBytes == 0 && n / blt::kSubPosBytes < (1ull << 31) - 8) {
+        // 32-bit chunk geometry in sub-tile units: a tile's first sub-tile index (below 2^31, a
+        // whole tile past the buffer's last included) divided by the chunk's sub-tiles
+        p.cs_subs = (uint32_t)std::min<uint64_t>(cs / blt::kSubPosBytes, 0x7FFFFFFFull);
+        p.cs_subs_magic = p.cs_subs > 1 ? (uint32_t)(0xFFFFFFFFull / p.cs_subs) : 0u;
     }
     p.allm = h->allmerge ? 1u : 0u;
     p.mark = h->mark | (h->mark << 16);
@@ -809,7 +818,10 @@ int run_pass(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8
         run->map_ready = scan16 && chain->next_scan;
     }
     p.ws_check = (ws_zeroed && !in_u16 && !chain) ? 1u : 0u;   // the caller's BLT_ENCODE_WORKSPACE_ZEROED
-    if (columnar) HIP_TRY(blt::launch_scan_bytes(p, h->byte_mode, (chain && h->live_first) ? 1 : 0, dev, s));
+    if (columnar) {
+        HIP_TRY(blt::launch_scan_bytes(p, h->byte_mode, byte_live, dev, s));
+        t_last_byte_tile = (uint32_t)tile;
+    }
     else if (scan16) {
         HIP_TRY(blt::launch_scan_tokens(p, ready ? 1 : 0, dev, s));
         ++t_last_scan_passes;
@@ -2102,6 +2114,9 @@ uint32_t blt_debug_last_u16_passes(void) { return t_last_u16_passes; }
 // Not in the public header: u16 passes the calling thread's last general-map encode enqueued on the
 // scan kernel (done or not).
 uint32_t blt_debug_last_scan_passes(void) { return t_last_scan_passes; }
+// Not in the public header: positions per tile of the byte-pass kernel the calling thread launched
+// last (49152: the headline instantiation of merges-file maps; 32768: the others; 0: none yet).
+uint32_t blt_debug_last_byte_tile(void) { return t_last_byte_tile; }
 
 // Not in the public header: a test hook that runs the kernels' device-error path (the one a
 // look-back timeout takes) for handle h on the current device and stream, setting error bit 1 in

@@ -12,7 +12,10 @@ constexpr uint64_t kTilePosU16 = kTilePos;     // positions per look-back tile o
 // 0.672 -> 0.804 ms, selfval 1.39 -> 1.77, multi 0.537 -> 0.575; profiles/r04_shift16_ab.txt)
 constexpr uint64_t kTilePosTok = 32768;        // tokens per look-back tile of the u16 scan kernel (32 wave ranges)
 constexpr uint64_t kTokRange = 1024;           // tokens per wave range (one chunk-map word each)
-constexpr uint64_t kTilePosBytes = 32768;      // positions per look-back tile of the byte-input pass
+constexpr uint64_t kTilePosBytes = 32768;      // byte-input pass: positions per status word of the workspace
+                                               // accounting (layout, reset, cover word, self-reset), whatever
+                                               // tile the launched instantiation takes (scan_bytes_subtiles)
+constexpr uint64_t kSubPosBytes = 16384;       // byte-input pass: positions per sub-tile (16 wave ranges of 1024)
 constexpr uint64_t kMinChunkBytes = 4096;      // byte pass needs chunk_size >= positions per wave range
 constexpr uint64_t kCtlBytes = 64;            // control block ahead of the status words
 constexpr uint32_t kCtlLeft = 15;             // ctl word: workgroups of a single-pass launch that have left
@@ -62,9 +65,9 @@ struct PassParams {
                                // arrays), zeroed here with its ticket word ctl[tick ^ kCtlTickAlt]
     uint32_t tick;             // ctl word of the tile tickets: 0, or kCtlTickAlt for odd chained u16 passes
     uint64_t cs_magic;         // cs > 0: floor((2^64 - 1) / cs), for x / cs by a high multiply
-    uint32_t cs_tiles;         // cs / kTilePosBytes when cs is a whole number of byte-pass tiles
-                               // (below 2^31), else 0
-    uint32_t cs_tiles_magic;   // floor((2^32 - 1) / cs_tiles) (cs_tiles > 1)
+    uint32_t cs_subs;          // cs / kSubPosBytes when cs is a whole number of byte-pass sub-tiles (and
+                               // the buffer holds fewer than 2^31 of them), else 0
+    uint32_t cs_subs_magic;    // floor((2^32 - 1) / cs_subs) (cs_subs > 1)
     uint32_t allm;             // byte pass: every byte pair is a merge (the entry's test is skipped)
     uint32_t mark;             // byte pass, mode 2: BE pattern (mark | mark << 16) of the high byte that
                                // marks a merge valued its own first byte
@@ -90,12 +93,19 @@ constexpr uint32_t kInjectFinish = 1u, kInjectScanTok = 2u, kInjectSparseMove = 
 // tokens with the bucket table (p.hbuckets) for the later passes of a general map; output BE.
 hipError_t launch_merge_pass(const PassParams& p, int input_u16, int big_endian, int device, hipStream_t s);
 // Byte-input pass (segment kernel, seg::scan_bytes_kernel), big-endian output: p.cs >=
-// kMinChunkBytes; tiles of kTilePosBytes positions.  mode: 0 every byte-pair merge value is >= 256,
+// kMinChunkBytes; tiles of scan_bytes_subtiles(mode, live) sub-tiles, and p.ntiles counts those
+// tiles.  mode: 0 every byte-pair merge value is >= 256,
 // so an entry's high byte tells a merge; 1 an entry that differs from the token of a is a merge; 2
 // as 1 with merges valued their own first byte marked (p.mark).  live (modes 1 and 2): the first
 // pass of a general map whose keys are byte pairs; it sets *p.done = kDoneBytePass when it made no
 // token below 256.
 hipError_t launch_scan_bytes(const PassParams& p, int mode, int live, int device, hipStream_t s);
+// Sub-tiles per tile of the instantiation launch_scan_bytes picks: the one place the host and the
+// launcher take a byte-pass launch's tile size from.  Mode 0 without the live bit (every merges
+// file: the headline kernel) runs 48 KiB tiles; the other instantiations spill VGPRs at three
+// sub-tiles and keep 32 KiB tiles.
+constexpr int scan_bytes_subtiles(int mode, int live) { return (mode == 0 && !live) ? 3 : 2; }
+constexpr uint64_t scan_bytes_tile(int mode, int live) { return (uint64_t)scan_bytes_subtiles(mode, live) * kSubPosBytes; }
 // done word value of a byte pass after which nothing merges (u16 pass k writes k)
 constexpr uint32_t kDoneBytePass = 0x80000000u;
 // u16 pass of a general map on the scan kernel (seg::scan_tokens_kernel), in place (p.in may equal

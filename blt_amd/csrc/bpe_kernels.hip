@@ -805,11 +805,13 @@ __device__ __forceinline__ void add2(uint32_t& a, uint32_t bit) {
     asm("v_lshl_add_u32 %0, %1, 1, %0" : "+v"(a) : "v"(bit));
 }
 
-// Workgroup geometry: 16 waves (4 per SIMD, 128 VGPRs each) times 2 sub-tiles per wave make one
-// 32 KiB tile.
+// Workgroup geometry: 16 waves (4 per SIMD, 128 VGPRs each) times NS sub-tiles per wave make one
+// tile: NS = 2 (32 KiB), or 3 (48 KiB) in the headline instantiation (scan_bytes_subtiles; the
+// byte-pass functions below take NS as a template parameter).
 constexpr int kThreads = 1024;
 constexpr int kWaves = kThreads / 64;
-constexpr int kS = 2;                                  // sub-tiles per tile
+constexpr int kS = 2;                                  // sub-tiles per tile (the default geometry)
+constexpr int kSMax = 3;                               // the largest instantiated
 // Cache policy (buffer aux bits) of the input loads and the output stores: nt (2).  Every input
 // byte is read once by one CU and every output byte written once: cfg3 0.604-0.613 -> 0.597-0.599 ms,
 // cfg5 0.815-0.818 -> 0.804 ms (config_rates, same box); cfg2's 100 MiB, replayed back to back,
@@ -817,7 +819,7 @@ constexpr int kS = 2;                                  // sub-tiles per tile
 constexpr int kLdPol = 2, kStPol = 2;
 constexpr uint32_t kWavePos = 64u * 16u;               // positions per wave per sub-tile
 constexpr uint64_t kSubPos = (uint64_t)kWaves * kWavePos;
-constexpr int kGroups = kS * kWaves;
+constexpr int kGroups = kS * kWaves;   // of the default geometry
 // Per-wave token stage: a wave range of 1024 positions emits 512..1024 tokens; the stage holds
 // 761 (2-byte aligned start + up to 1522 bytes), all the LDS the table leaves: every range of text
 // or random bytes under a large merge map (~580 tokens).  A range with more tokens goes through it
@@ -827,11 +829,13 @@ constexpr int kStageWave = 1536;    // the LDS the table leaves, shared by the w
 // through register spills than the extra round trips they save.)
 constexpr int kLbWin = 1;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-static_assert(kSubPos * kS == kTilePosBytes, "tile geometry");
+static_assert(kSubPos == kSubPosBytes, "sub-tile geometry");
 static_assert(kWavePos <= kMinChunkBytes, "at most one chunk end per wave sub-tile");
-static_assert(kGroups <= 64, "one lane per group in the tile resolve");
+static_assert(kSMax * kWaves <= 64, "one lane per group in the tile resolve");
+static_assert((uint64_t)kSMax * kSubPos < 65536u, "a tile's token counts fit the packed 16-bit scan");
 static_assert(kStageWave % 16 == 0, "stage alignment");
-static_assert((uint64_t)kS * kSubPos == kTilePosBytes, "tile = kS sub-tiles");
+static_assert((uint64_t)kS * kSubPos == kTilePosBytes, "the default tile is the workspace's accounting unit");
+static_assert(scan_bytes_subtiles(0, 0) <= kSMax && scan_bytes_subtiles(1, 1) == kS, "instantiated geometries");
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ uint64_t uni64(uint64_t v) {
@@ -893,25 +897,31 @@ struct TInfo {
 };
 
 // The chunk geometry of tile T (every wave computes it for its own tiles: SALU work, no LDS).
-// When the chunk size is a whole number of tiles (every chunk size of the configs: 16 MiB = 512
-// tiles), T / (cs / tile) by a 32-bit high multiply with the host's reciprocal and at most two
+// When the chunk size is a whole number of sub-tiles (every chunk size of the configs: 16 MiB =
+// 1024 sub-tiles; a 48 KiB tile does not divide it, a sub-tile does), the tile's first sub-tile
+// NS T divided by cs / sub-tile: a 32-bit high multiply with the host's reciprocal and at most two
 // corrections; otherwise tile0 / cs by a 64-bit high multiply.
 // "No chunk start in this tile or the first wave range after it": two tiles from the tile start
 // (chunk starts and chunk sizes are capped there, so a range's one-past-the-end test never fires).
-constexpr uint32_t kFarPos = 2u * (uint32_t)kTilePosBytes;
+template <int NS>
+constexpr uint32_t kTileBytes = (uint32_t)NS * (uint32_t)kSubPos;
+template <int NS>
+constexpr uint32_t kFarPos = 2u * kTileBytes<NS>;
+template <int NS>
 __device__ __forceinline__ TInfo tile_info(const PassParams& p, uint32_t T) {
     TInfo t;
-    const uint64_t tile0 = (uint64_t)T * kTilePosBytes;
+    const uint64_t tile0 = (uint64_t)T * kTileBytes<NS>;
     const uint64_t left = p.n > tile0 ? p.n - tile0 : 0;
     t.rn = (uint32_t)(left > 0x7FFFFFFFull ? 0x7FFFFFFFull : left);
-    if (p.cs_tiles) {
-        const uint32_t d = p.cs_tiles;
-        uint32_t q = d == 1u ? T : __umulhi(T, p.cs_tiles_magic);
-        uint32_t r = T - q * d;
+    if (p.cs_subs) {
+        const uint32_t d = p.cs_subs;
+        const uint32_t S = (uint32_t)NS * T;   // (the host: fewer than 2^31 sub-tiles in the buffer)
+        uint32_t q = d == 1u ? S : __umulhi(S, p.cs_subs_magic);
+        uint32_t r = S - q * d;
         if (r >= d) { q += 1u; r -= d; }
         if (r >= d) { q += 1u; r -= d; }
-        const uint32_t left_tiles = r ? d - r : 0u;   // tiles to the next chunk start
-        t.bge = left_tiles > 2u ? kFarPos : left_tiles * (uint32_t)kTilePosBytes;
+        const uint32_t left_subs = r ? d - r : 0u;   // sub-tiles to the next chunk start
+        t.bge = left_subs > 2u * (uint32_t)NS ? kFarPos<NS> : left_subs * (uint32_t)kSubPos;
         t.k0 = (uint64_t)q + (r ? 1u : 0u);
         return t;
     }
@@ -921,7 +931,7 @@ __device__ __forceinline__ TInfo tile_info(const PassParams& p, uint32_t T) {
     if (r >= cs) { q += 1; r -= cs; }
     if (r >= cs) { q += 1; r -= cs; }
     const uint64_t d = r ? cs - r : 0;
-    t.bge = (uint32_t)(d > kFarPos ? kFarPos : d);
+    t.bge = (uint32_t)(d > kFarPos<NS> ? kFarPos<NS> : d);
     t.k0 = q + (r ? 1u : 0u);
     return t;
 }
@@ -994,7 +1004,7 @@ __device__ __forceinline__ void lane_wave_fns(const uint32_t (&m)[NS], uint32_t 
 }
 
 // ---- phase 1 of a tile: lookups, lane functions, wave functions ------------------------------
-// Three straight-line passes over the kS sub-tiles (lookups; the rare uniform fix-up of buffer
+// Three straight-line passes over the NS sub-tiles (lookups; the rare uniform fix-up of buffer
 // and chunk ends; lane functions and wave resolves), so the scheduler can overlap sub-tiles.
 // kMode (the merge test of a self-token entry): 0 (kHiM) a merge value is >= 256, so "merge" is the
 // entry's high byte; 1 the entry differs from the token of a itself; 2 as 1, and merges valued their
@@ -1003,16 +1013,20 @@ __device__ __forceinline__ void lane_wave_fns(const uint32_t (&m)[NS], uint32_t 
 // listing all 65 536 pairs), whatever the entry.  kLive: the lane also reports whether one of its
 // merges (surviving buffer and chunk ends) made a token below 256, the only key components of a
 // map whose keys are byte pairs: a first pass with none is the fixpoint (see scan_bytes_kernel).
-template <bool kBE, int kMode, bool kLive>
-__device__ __forceinline__ void phase1_tile(uint32_t tab, const uint32_t (&x)[kS][4], const uint32_t (&nxt)[kS],
-                                            const TInfo& ti, uint32_t cs32, uint32_t wave, int lane,
-                                            TileState& st, uint32_t (*wfn)[4], uint32_t allm, uint32_t mark,
-                                            uint64_t* sub = nullptr) {
+// kXEarly (the 48 KiB geometry, mode 0): x_dead(j) is called as soon as sub-tile j's lookups are
+// issued, and refills x[j] and nxt[j] in place with the next tile's bytes; the rare fix-ups then
+// read the one or two raw bytes they need from memory again (tile T of the input).
+template <bool kBE, int kMode, bool kLive, int NS, bool kXEarly, typename XDead>
+__device__ __forceinline__ void phase1_tile(const PassParams& p, uint32_t T, uint32_t tab, const uint32_t (&x)[NS][4],
+                                            const uint32_t (&nxt)[NS], const TInfo& ti, uint32_t cs32, uint32_t wave,
+                                            int lane, TileStateT<NS>& st, uint32_t (*wfn)[4], uint32_t allm,
+                                            uint32_t mark, uint64_t* sub, XDead&& x_dead) {
     static_assert(kBE, "the byte pass writes big-endian tokens");
     static_assert(kMode >= 0 && kMode <= 2 && !(kLive && kMode == 0), "phase-1 mode");
-    uint32_t m[kS];
+    static_assert(!kXEarly || kMode == 0, "modes 1 and 2 read x for their merge test");
+    uint32_t m[NS];
 #pragma unroll
-    for (int j = 0; j < kS; ++j) {
+    for (int j = 0; j < NS; ++j) {
         // right neighbour of position 15: next lane's first byte (wave_shl:1); lane 63 keeps
         // the "old" operand, the byte after the wave's range (byte 0 of nbw; bytes 1..3 unused)
         const uint32_t nbw = (uint32_t)__builtin_amdgcn_update_dpp((int)nxt[j], (int)x[j][0], 0x130, 0xF, 0xF, false);
@@ -1034,6 +1048,7 @@ __device__ __forceinline__ void phase1_tile(uint32_t tab, const uint32_t (&x)[kS
             }
             st.v[j][h] = __builtin_amdgcn_perm(vb, va, 0x05040100u);   // va | vb << 16, one op
         }
+        if constexpr (kXEarly) x_dead(j);
         uint32_t m32 = 0;   // even positions in bits 0..14, odd positions in bits 16..30
 #pragma unroll
         for (int h = 0; h < 8; ++h) {
@@ -1060,7 +1075,7 @@ __device__ __forceinline__ void phase1_tile(uint32_t tab, const uint32_t (&x)[kS
     // buffer end and chunk ends (uniform per wave range; rare)
     uint32_t bnext = ti.bge;   // first chunk start > the wave range's first position
 #pragma unroll
-    for (int j = 0; j < kS; ++j) {
+    for (int j = 0; j < NS; ++j) {
         const uint32_t wrel = (uint32_t)j * (uint32_t)kSubPos + wave * kWavePos;
         while (bnext <= wrel) bnext += cs32;   // uniform; kSubPos / 4096 steps at most
         const uint32_t rem = ti.rn > wrel ? ti.rn - wrel : 0u;
@@ -1071,16 +1086,28 @@ __device__ __forceinline__ void phase1_tile(uint32_t tab, const uint32_t (&x)[kS
             const uint32_t vmask = r >= 16 ? 0xFFFFu : (r <= 0 ? 0u : ((1u << r) - 1u));
             uint32_t mm = m[j] & ((vmask >> 1) | (r > 16 ? 0x8000u : 0u));
             uint32_t forced = (r >= 1 && r <= 16) ? (1u << (r - 1)) : 0u;   // the buffer's last position
+            uint32_t e = 16u;
             if (has_end) {                                                   // chunk end b - 1 here
-                const uint32_t e = bnext - 1u - wrel - l16;
+                e = bnext - 1u - wrel - l16;
                 if (e < 16u) { mm &= ~(1u << e); forced |= 1u << e; }
             }
             if (__ballot(forced != 0)) {   // a cut merge emits its raw byte
+                uint32_t b1 = 0, b2 = 0;   // kXEarly: the bytes at the buffer's last position and the chunk end
+                if constexpr (kXEarly) {
+                    const uint64_t tile0 = (uint64_t)T * kTileBytes<NS>;
+                    const __amdgpu_buffer_rsrc_t rs =
+                        rsrc_at(reinterpret_cast<const uint8_t*>(KARG(in)) + tile0, p.n > tile0 ? p.n - tile0 : 0);
+                    const uint32_t o = wrel + l16, oob = 0x80000000u;   // (past every resource's records: reads 0)
+                    b1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)((r >= 1 && r <= 16) ? o + (uint32_t)(r - 1) : oob), 0, 0);
+                    b2 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)(e < 16u ? o + e : oob), 0, 0);
+                }
 #pragma unroll
                 for (int h = 0; h < 8; ++h) {
                     const uint32_t xw = x[j][h >> 1];
-                    const uint32_t raw = __builtin_amdgcn_perm(xw, xw, kBE ? ((h & 1) ? 0x030C020Cu : 0x010C000Cu)
-                                                                           : ((h & 1) ? 0x0C030C02u : 0x0C010C00u));
+                    const uint32_t raw = kXEarly ? ((((uint32_t)(2 * h) == e ? b2 : b1) & 0xFFu) << 8) |
+                                                       ((((uint32_t)(2 * h + 1) == e ? b2 : b1) & 0xFFu) << 24)
+                                                 : __builtin_amdgcn_perm(xw, xw, kBE ? ((h & 1) ? 0x030C020Cu : 0x010C000Cu)
+                                                                                     : ((h & 1) ? 0x0C030C02u : 0x0C010C00u));
                     const uint32_t fm = (((forced >> (2 * h)) & 1u) ? 0x0000FFFFu : 0u) |
                                         (((forced >> (2 * h + 1)) & 1u) ? 0xFFFF0000u : 0u);
                     st.v[j][h] = (st.v[j][h] & ~fm) | (raw & fm);
@@ -1092,11 +1119,12 @@ __device__ __forceinline__ void phase1_tile(uint32_t tab, const uint32_t (&x)[kS
             st.mv[j] = m[j] | 0xFFFF0000u;
         }
     }
+    if constexpr (!kXEarly) x_dead(0);
     uint32_t wlive = 0;
     if (kLive) {   // a surviving merge whose token is below 256 (BE high byte 0)
         uint32_t lv = 0;
 #pragma unroll
-        for (int j = 0; j < kS; ++j) {
+        for (int j = 0; j < NS; ++j) {
             uint32_t low32 = 0;   // as m32: even positions in bits 0..14, odd in 16..30
 #pragma unroll
             for (int h = 0; h < 8; ++h) low32 |= (pk_nz(st.v[j][h] & 0x00FF00FFu) ^ 0x00010001u) << (2 * h);
@@ -1108,7 +1136,7 @@ __device__ __forceinline__ void phase1_tile(uint32_t tab, const uint32_t (&x)[kS
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         sub[0] = __builtin_amdgcn_s_memtime();
     }
-    lane_wave_fns<kS>(m, wave, lane, st, wfn, wlive);
+    lane_wave_fns<NS>(m, wave, lane, st, wfn, wlive);
     if (sub) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         sub[1] = __builtin_amdgcn_s_memtime();
@@ -1506,9 +1534,15 @@ struct SparseRange {
 
 // Tile-level: carry-in C, O tokens before the tile; the output resource starts at the 16-byte
 // boundary at or below byte 2 O, so every offset below is 32-bit.
+// NS = 2: every range's offsets first, then the sparse ranges' stage and copy-out, so one range's
+// scan overlaps another's stores.  NS = 3: each sparse range goes out as soon as its offsets are
+// known; keeping three ranges' masks and offsets live across the loop costs the registers the
+// 48 KiB geometry does not have.
+template <int NS>
 __device__ __forceinline__ void emit_tile(const PassParams& p, uint32_t Tp, const TInfo& ti, uint32_t cs32,
-                                          uint32_t wave, int lane, const TileState& st, const uint32_t (*gin)[4],
+                                          uint32_t wave, int lane, const TileStateT<NS>& st, const uint32_t (*gin)[4],
                                           uint32_t C, uint64_t O, uint8_t* stg, bool has_coff) {
+    constexpr bool kInline = NS > kS;
     uint8_t* out = reinterpret_cast<uint8_t*>(KARG(out));   // (reloaded per tile: fewer live SGPRs)
     const uint64_t out_cap = KARG(out_cap);
     const uint64_t obase = (2ull * O) & ~15ull;
@@ -1517,10 +1551,28 @@ __device__ __forceinline__ void emit_tile(const PassParams& p, uint32_t Tp, cons
     const uint32_t stg_lds = lds_addr(stg);
     uint32_t cnext = ti.bge;   // first chunk start >= the wave range's first position
     uint64_t kc = ti.k0;       // its chunk index
-    SparseRange sr[kS];
-    bool sparse[kS];
+    SparseRange sr[NS];
+    bool sparse[NS];
+    // Stage -> global in one part, or in two (lanes 0..31, then 32..63: at most 512 tokens
+    // each) when the range's tokens overflow the stage (few merges, e.g. random bytes).
+    auto emit_sparse = [&](int j) {
+        const uint32_t two = (sr[j].gb & 15u) + 2u * sr[j].wcnt <= (uint32_t)kStageWave ? 0u : 1u;
+        const uint32_t off32 = two ? uni(lane_u32(sr[j].lane_off, 32)) : 0u;   // tokens before lane 32
+        for (uint32_t part = 0; part <= two; ++part) {
+            const uint32_t base = part ? off32 : 0u;
+            const uint32_t cnt = two ? (part ? sr[j].wcnt - off32 : off32) : sr[j].wcnt;
+            const uint32_t gbp = sr[j].gb + 2u * base;
+            if (!two || ((uint32_t)lane >> 5) == part) {
+                stage_b16(st.v[j], sr[j].L, stg_lds + (gbp & 15u) + 2u * (sr[j].lane_off - base));
+            }
+            const CopyPart cp = {gbp & ~15u, gbp & 15u, (gbp & 15u) + 2u * cnt};
+            CopyData<> d;
+            copy_read(stg, cp, lane, d);
+            copy_store(ro, cp, lane, d);
+        }
+    };
 #pragma unroll
-    for (int j = 0; j < kS; ++j) {
+    for (int j = 0; j < NS; ++j) {
         const uint32_t g = (uint32_t)j * kWaves + wave;
         const uint32_t wrel = (uint32_t)j * (uint32_t)kSubPos + wave * kWavePos;
         const uint32_t cg = uni(gin[g][C]);
@@ -1553,27 +1605,12 @@ __device__ __forceinline__ void emit_tile(const PassParams& p, uint32_t Tp, cons
         sr[j].lane_off = lane_off;
         sr[j].gb = gb;
         sr[j].wcnt = uni(lane_u32(lane_off + __popc(L), 63));
+        if constexpr (kInline) emit_sparse(j);
     }
-    auto fits = [&](int j) { return (sr[j].gb & 15u) + 2u * sr[j].wcnt <= (uint32_t)kStageWave; };
+    if constexpr (!kInline) {
 #pragma unroll
-    for (int j = 0; j < kS; ++j) {
-        if (!sparse[j]) continue;
-        // Stage -> global in one part, or in two (lanes 0..31, then 32..63: at most 512 tokens
-        // each) when the range's tokens overflow the stage (few merges, e.g. random bytes).
-        const uint32_t two = fits(j) ? 0u : 1u;
-        const uint32_t off32 = two ? uni(lane_u32(sr[j].lane_off, 32)) : 0u;   // tokens before lane 32
-        for (uint32_t part = 0; part <= two; ++part) {
-            const uint32_t base = part ? off32 : 0u;
-            const uint32_t cnt = two ? (part ? sr[j].wcnt - off32 : off32) : sr[j].wcnt;
-            const uint32_t gbp = sr[j].gb + 2u * base;
-            if (!two || ((uint32_t)lane >> 5) == part) {
-                stage_b16(st.v[j], sr[j].L, stg_lds + (gbp & 15u) + 2u * (sr[j].lane_off - base));
-            }
-            const CopyPart cp = {gbp & ~15u, gbp & 15u, (gbp & 15u) + 2u * cnt};
-            CopyData<> d;
-            copy_read(stg, cp, lane, d);
-            copy_store(ro, cp, lane, d);
-        }
+        for (int j = 0; j < NS; ++j)
+            if (sparse[j]) emit_sparse(j);
     }
 }
 
@@ -1583,16 +1620,17 @@ __device__ __forceinline__ void emit_tile(const PassParams& p, uint32_t Tp, cons
 // holding the buffer end, the lanes' bytes again one by one.  Keeping the common path free of
 // branches lets the loads land in x directly: a branch that merges x would make the compiler
 // wait for them right here.
+template <int NS>
 __device__ __forceinline__ void load_tile(const PassParams& p, uint32_t Tn, uint32_t wave, int lane,
-                                          uint32_t (&x)[kS][4], uint32_t (&nxt)[kS]) {
+                                          uint32_t (&x)[NS][4], uint32_t (&nxt)[NS]) {
     const uint8_t* in = reinterpret_cast<const uint8_t*>(KARG(in));   // (reloaded per tile)
-    const uint64_t tile0 = (uint64_t)Tn * kTilePosBytes;
+    const uint64_t tile0 = (uint64_t)Tn * kTileBytes<NS>;
     const uint64_t left = p.n > tile0 ? p.n - tile0 : 0;
     const __amdgpu_buffer_rsrc_t r = rsrc_at(in + tile0, left);
     const __amdgpu_buffer_rsrc_t rd = rsrc_at(in + tile0, left & ~3ull);
     const uint32_t rn = (uint32_t)(left > 0x7FFFFFFFull ? 0x7FFFFFFFull : left);
 #pragma unroll
-    for (int j = 0; j < kS; ++j) {
+    for (int j = 0; j < NS; ++j) {
         const uint32_t wrel = (uint32_t)j * (uint32_t)kSubPos + wave * kWavePos;
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(rd, (int)wrel + 16 * lane, 0, kLdPol);
         x[j][0] = v[0]; x[j][1] = v[1]; x[j][2] = v[2]; x[j][3] = v[3];
@@ -1602,7 +1640,7 @@ __device__ __forceinline__ void load_tile(const PassParams& p, uint32_t Tn, uint
         nxt[j] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rd, (int)(wrel + kWavePos), 0, 0);
     }
 #pragma unroll
-    for (int j = 0; j < kS; ++j) {
+    for (int j = 0; j < NS; ++j) {
         const uint32_t wrel = (uint32_t)j * (uint32_t)kSubPos + wave * kWavePos;
         if (rn > wrel && rn - wrel < kWavePos + 16u) {   // uniform: the buffer end is near this range
             nxt[j] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)(wrel + kWavePos), 0, 0);
@@ -1615,6 +1653,31 @@ __device__ __forceinline__ void load_tile(const PassParams& p, uint32_t Tn, uint
                          << (8 * b);
                 x[j][q] = d;
             }
+        }
+    }
+}
+
+// One sub-tile of load_tile (the in-place refill of the 48 KiB geometry, issued from phase 1): rd
+// and rn as there, computed once per tile by the caller.
+template <int NS>
+__device__ __forceinline__ void load_sub(const PassParams& p, uint32_t Tn, __amdgpu_buffer_rsrc_t rd, uint32_t rn, int j,
+                                         uint32_t wave, int lane, uint32_t (&x)[4], uint32_t& nxt) {
+    const uint32_t wrel = (uint32_t)j * (uint32_t)kSubPos + wave * kWavePos;
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rd, (int)wrel + 16 * lane, 0, kLdPol);
+    x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+    nxt = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rd, (int)(wrel + kWavePos), 0, 0);
+    if (rn > wrel && rn - wrel < kWavePos + 16u) {   // uniform: the buffer end is near this range
+        const uint64_t tile0 = (uint64_t)Tn * kTileBytes<NS>;
+        const __amdgpu_buffer_rsrc_t r =
+            rsrc_at(reinterpret_cast<const uint8_t*>(KARG(in)) + tile0, p.n > tile0 ? p.n - tile0 : 0);
+        nxt = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)(wrel + kWavePos), 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t d = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                d |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)wrel + 16 * lane + 4 * q + b, 0, 0) << (8 * b);
+            x[q] = d;
         }
     }
 }
@@ -1671,12 +1734,25 @@ __device__ __forceinline__ void wait_ge(const PassParams& p, const uint32_t* f, 
 // marks the pass final (done = kDoneBytePass) when no tile had one: every later pass would merge
 // nothing (a pair this pass left alone was looked up and rejected; a token >= 256 is in no key),
 // so the u16 passes the host enqueued behind it return at once.
-template <bool kBE, int kMode, bool kLive>
+//
+// NS sub-tiles per tile.  NS = 3 (48 KiB tiles, the headline instantiation): an iteration's fixed
+// cost (the load, look-back and hand-over round trips) is spread over half as many bytes again.
+// At 128 VGPRs there is no room for a second input buffer, so Tq's bytes are loaded into T's own
+// registers sub-tile by sub-tile, as soon as phase 1 has issued that sub-tile's lookups (the rare
+// chunk- and buffer-end fix-ups read their raw bytes from memory again), and land during the rest
+// of phase 1, the look-back wait and Tp's emission.
+template <bool kBE, int kMode, bool kLive, int NS>
 __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
+    constexpr int kG = NS * kWaves;       // groups (wave ranges) per tile
+    constexpr bool kInPlace = NS > kS;    // one input buffer, refilled in place
+    static_assert(!kInPlace || kMode == 0, "in-place refill: phase 1 must not read x after its lookups");
+    // the look-back's lane index and 32-bit tile indices computed where they are used (see lb_issue):
+    // kInPlace has no registers for the hoisted per-lane constants either
+    constexpr bool kLbFresh = kMode != 0 || kInPlace;
     __shared__ __attribute__((aligned(16))) uint16_t s_tab[kSelfEntries];
     __shared__ __attribute__((aligned(16))) uint8_t s_stage[kWaves][kStageWave];
-    __shared__ __attribute__((aligned(16))) uint32_t s_wfn[kRing][kGroups][4];   // wave functions (phase 1)
-    __shared__ uint32_t s_gin[kRing][kGroups][4];   // group carry-in |H=0,1, offset |H=0,1
+    __shared__ __attribute__((aligned(16))) uint32_t s_wfn[kRing][kG][4];   // wave functions (phase 1)
+    __shared__ uint32_t s_gin[kRing][kG][4];   // group carry-in |H=0,1, offset |H=0,1
     __shared__ uint32_t s_tfn[kRing][4];            // tile co0, co1, tot0, tot1
     __shared__ uint64_t s_O[kRing];                 // tokens before the tile
     __shared__ uint32_t s_C[kRing];                 // carry into the tile (2: failed tile, no output)
@@ -1692,7 +1768,10 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
     const uint32_t wave = uni((uint32_t)tid >> 6);
     const uint64_t n = p.n;
     const uint32_t ntiles = p.ntiles;
-    const uint32_t cs32 = (uint32_t)(p.cs > kFarPos ? kFarPos : p.cs);
+    const uint32_t cs32 = (uint32_t)(p.cs > kFarPos<NS> ? kFarPos<NS> : p.cs);
+    // status words of the workspace's accounting (one per kTilePosBytes positions): the refuse rule
+    // and the self-reset count these, whatever the tile; the kernel uses the first ntiles of them
+    const uint32_t ws_words = NS == kS ? ntiles : (uint32_t)((n + kTilePosBytes - 1) / kTilePosBytes);
     const uint32_t allm = uni(p.allm), mark = uni(p.mark);
     const bool has_coff = p.chunk_off != nullptr;   // (the pointer itself is reloaded where stored)
 
@@ -1732,30 +1811,39 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
     uint32_t T = uni(s_tk[kRing - 2]);    // tile in phase 1
     uint32_t Tp = kNone;                  // tile waiting for emission
     uint32_t Tq = uni(s_tk[kRing - 1]);   // the tile after T (its bytes load during T's iteration)
-    if (ws_refused(p, ntiles, cover)) T = kNone;   // (its two tickets are dropped: the reset zeroes them)
+    if (ws_refused(p, ws_words, cover)) T = kNone;   // (its two tickets are dropped: the reset zeroes them)
     if (T >= ntiles || Tq >= ntiles) Tq = kNone;
     TInfo ti = {}, tip = {};
-    if (T < ntiles) ti = tile_info(p, T);
+    if (T < ntiles) ti = tile_info<NS>(p, T);
     __syncthreads();
 
-    uint32_t xa[kS][4], xb[kS][4];   // input bytes of each sub-tile: T's, and Tq's (ping-pong)
-    uint32_t na[kS], nb[kS];         // byte after each wave range (lane 63's right neighbour)
-    if (T < ntiles) load_tile(p, T, wave, lane, xa, na);
-    TileState sa, sb;       // phase-1 states: T's and Tp's (ping-pong)
+    uint32_t xa[NS][4], xb[NS][4];   // input bytes of each sub-tile: T's, and Tq's (ping-pong; kInPlace: xa only)
+    uint32_t na[NS], nb[NS];         // byte after each wave range (lane 63's right neighbour)
+    if (T < ntiles) load_tile<NS>(p, T, wave, lane, xa, na);
+    TileStateT<NS> sa, sb;   // phase-1 states: T's and Tp's (ping-pong)
     uint64_t lbs[kLbWin];   // look-back wave: status words for the pending tile's look-back
     uint32_t it = 0;
 
     // One iteration: phase 1 of T from `x` into `sc`, emission of Tp from `sp`, Tq's bytes into
     // `xq`.  The loop runs it twice per trip with the roles swapped, so no state is copied.
-    auto step = [&](uint32_t (&x)[kS][4], uint32_t (&nxt)[kS], uint32_t (&xq)[kS][4], uint32_t (&nxtq)[kS],
-                    TileState& sc, const TileState& sp) {
+    auto step = [&](uint32_t (&x)[NS][4], uint32_t (&nxt)[NS], uint32_t (&xq)[NS][4], uint32_t (&nxtq)[NS],
+                    TileStateT<NS>& sc, const TileStateT<NS>& sp) {
         const uint32_t slot = it & (kRing - 1), pslot = (it - 1) & (kRing - 1);
         uint64_t stamp[7], sub[2] = {0, 0};
         const bool stamping = kTiming && p.debug != nullptr;
         if (stamping) stamp[0] = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): T's bytes have landed
         if (stamping) stamp[1] = __builtin_amdgcn_s_memtime();
-        if (Tq < ntiles) load_tile(p, Tq, wave, lane, xq, nxtq);   // a whole iteration to land
+        // Tq's bytes: a whole iteration to land, or (kInPlace: xq is x) issued from phase 1 below
+        if (!kInPlace && Tq < ntiles) load_tile<NS>(p, Tq, wave, lane, xq, nxtq);
+        // kInPlace: Tq's descriptor (whole dwords) and length now, off phase 1's LDS wait counter
+        uint64_t q0 = 0, qleft = 0;
+        if (kInPlace && Tq < ntiles) {
+            q0 = (uint64_t)Tq * kTileBytes<NS>;
+            qleft = n > q0 ? n - q0 : 0;
+        }
+        const __amdgpu_buffer_rsrc_t rdq = rsrc_at(reinterpret_cast<const uint8_t*>(KARG(in)) + q0, qleft & ~3ull);
+        const uint32_t rnq = (uint32_t)(qleft > 0x7FFFFFFFull ? 0x7FFFFFFFull : qleft);
         // the tile after Tq, claimed now: claimed one phase before its bytes are needed, so claim
         // order stays close to publish order (a tile claimed further ahead lands behind
         // later-claimed ones and stalls their look-backs)
@@ -1770,8 +1858,11 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
             // phase 1 last and so hold back the tile's resolve and aggregate (which successors'
             // look-backs wait for), and finish emission last (which holds back their next phase 1)
             if (wave >= (uint32_t)kPrioP1Wave) __builtin_amdgcn_s_setprio(kPrioP1);
-            phase1_tile<kBE, kMode, kLive>(tab, x, nxt, ti, cs32, wave, lane, sc, s_wfn[slot], allm, mark,
-                                           stamping ? sub : nullptr);
+            phase1_tile<kBE, kMode, kLive, NS, kInPlace>(
+                p, T, tab, x, nxt, ti, cs32, wave, lane, sc, s_wfn[slot], allm, mark, stamping ? sub : nullptr, [&](int j) {
+                    // (no tile after T: a descriptor of 0 records, the loads read zeros nobody uses)
+                    if constexpr (kInPlace) load_sub<NS>(p, Tq, rdq, rnq, j, wave, lane, xq[j], nxtq[j]);
+                });
             __builtin_amdgcn_s_setprio(0);
             uint32_t old = 0;
             if (lane == 0)
@@ -1779,7 +1870,7 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
             old = uni(old);
             lbw = old == (uint32_t)kWaves * (it / kRing);
             if (old == (uint32_t)kWaves * (it / kRing + 1u) - 1u) {
-                resolve_tile<kGroups, kLive, kMode != 0>(p, T, lane, s_wfn[slot], s_gin[slot], s_tfn[slot]);
+                resolve_tile<kG, kLive, kLbFresh>(p, T, lane, s_wfn[slot], s_gin[slot], s_tfn[slot]);
                 if (lane == 0) lds_release(&s_rdone, it + 1u);
                 if (stamping && lane == 0) p.debug[4ull * ntiles + 4ull * T] = __builtin_amdgcn_s_memrealtime();
             }
@@ -1792,19 +1883,19 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
             uint32_t C = 1u, how = 0xFFFFu, spins = 0, bad = 0, live = 0;
             uint64_t O = 0ull;
             const bool lb = Tp > 0;
-            if (lb) lb_issue<kMode != 0>(p, (int64_t)Tp - 1, lane, lbs);
+            if (lb) lb_issue<kLbFresh>(p, (int64_t)Tp - 1, lane, lbs);
             const uint64_t rt_snap = stamping ? __builtin_amdgcn_s_memrealtime() : 0;
             // Tp was resolved last iteration: its tile function is read while the snapshot flies
             wait_ge(p, &s_rdone, it);
             const uint32_t tfl = uni(s_tfn[pslot][0]), tf1 = uni(s_tfn[pslot][1]);
             const uint32_t tf0 = tfl & 1u, tf2 = uni(s_tfn[pslot][2]), tf3 = uni(s_tfn[pslot][3]);
-            if (lb) lb_finish<kMode != 0>(p, Tp, lane, lbs, C, O, how, spins, live, kTiming ? &bad : nullptr);
+            if (lb) lb_finish<kLbFresh>(p, Tp, lane, lbs, C, O, how, spins, live, kTiming ? &bad : nullptr);
             live |= (tfl >> 1) & 1u;   // tiles up to and including Tp (kLive; 0 otherwise)
             if (lane == 0) {
                 const uint64_t end = O + (C == 1u ? tf3 : tf2);
                 // a failed tile (flagged) writes nothing (C = 2) and publishes a prefix only so its
                 // successors finish
-                if (C > 1u || O > (uint64_t)Tp * kTilePosBytes || end > n) {
+                if (C > 1u || O > (uint64_t)Tp * kTileBytes<NS> || end > n) {
                     if (C <= 1u) record_error(p, 4u, Tp, 0xFFu, O, end, C);
                     O = 0; C = 2u;
                 }
@@ -1844,7 +1935,7 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
             if (wave >= (uint32_t)kPrioEmWave) __builtin_amdgcn_s_setprio(kPrioEm);
             const uint32_t Cp = uni(s_C[pslot]);
             if (Cp <= 1u)   // C = 2: a failed tile (flagged), no output
-                emit_tile(p, Tp, tip, cs32, wave, lane, sp, s_gin[pslot], Cp, uni64(s_O[pslot]), s_stage[wave], has_coff);
+                emit_tile<NS>(p, Tp, tip, cs32, wave, lane, sp, s_gin[pslot], Cp, uni64(s_O[pslot]), s_stage[wave], has_coff);
             __builtin_amdgcn_s_setprio(0);
         }
         if (stamping) stamp[5] = __builtin_amdgcn_s_memtime();
@@ -1873,7 +1964,7 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
             if (Tr >= ntiles) Tr = kNone;
         }
         tip = ti;
-        if (Tq < ntiles) ti = tile_info(p, Tq);
+        if (Tq < ntiles) ti = tile_info<NS>(p, Tq);
         Tp = T;
         T = Tq;
         Tq = Tr;
@@ -1881,13 +1972,13 @@ __global__ __launch_bounds__(kThreads) void scan_bytes_kernel(PassParams p) {
     };
     for (;;) {
         if (!(T < ntiles || Tp < ntiles)) break;
-        step(xa, na, xb, nb, sa, sb);
+        if constexpr (kInPlace) step(xa, na, xa, na, sa, sb); else step(xa, na, xb, nb, sa, sb);
         if (!(T < ntiles || Tp < ntiles)) break;
-        step(xb, nb, xa, na, sb, sa);
+        if constexpr (kInPlace) step(xa, na, xa, na, sb, sa); else step(xb, nb, xa, na, sb, sa);
     }
     if (wg_rec && lane == 0)
         atomicMax(reinterpret_cast<unsigned long long*>(wg_rec + 2), (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    self_reset(p, ntiles, &s_tkdone);
+    self_reset(p, ws_words, &s_tkdone);
 }
 
 // ===========================================================================================
@@ -3171,18 +3262,21 @@ hipError_t launch_merge_pass(const PassParams& p, int input_u16, int big_endian,
 hipError_t launch_scan_bytes(const PassParams& p, int mode, int live, int device, hipStream_t s) {
     if (p.ntiles == 0) return hipSuccess;
     using seg::scan_bytes_kernel;
-    const void* fn = mode == 0 ? (const void*)scan_bytes_kernel<true, 0, false>
-                     : mode == 1 ? (live ? (const void*)scan_bytes_kernel<true, 1, true> : (const void*)scan_bytes_kernel<true, 1, false>)
-                                 : (live ? (const void*)scan_bytes_kernel<true, 2, true> : (const void*)scan_bytes_kernel<true, 2, false>);
     if (mode < 0 || mode > 2 || (mode == 0 && live)) return hipErrorInvalidValue;
+    constexpr int kS0 = scan_bytes_subtiles(0, 0), kSx = seg::kS;   // the instantiated geometries
+    if (scan_bytes_subtiles(mode, live) != (mode == 0 ? kS0 : kSx)) return hipErrorInvalidValue;
+    if (p.ntiles != (p.n + scan_bytes_tile(mode, live) - 1) / scan_bytes_tile(mode, live)) return hipErrorInvalidValue;
+    const void* fn = mode == 0 ? (const void*)scan_bytes_kernel<true, 0, false, kS0>
+                     : mode == 1 ? (live ? (const void*)scan_bytes_kernel<true, 1, true, kSx> : (const void*)scan_bytes_kernel<true, 1, false, kSx>)
+                                 : (live ? (const void*)scan_bytes_kernel<true, 2, true, kSx> : (const void*)scan_bytes_kernel<true, 2, false, kSx>);
     // every byte-pass instantiation holds the whole LDS: one workgroup per CU, one cache entry
     const int grid = grid_for(p.ntiles, device, fn, seg::kThreads, 4);
     const dim3 g((unsigned)grid), b(seg::kThreads);
-    if (mode == 0) hipLaunchKernelGGL((scan_bytes_kernel<true, 0, false>), g, b, 0, s, p);
-    else if (mode == 1 && live) hipLaunchKernelGGL((scan_bytes_kernel<true, 1, true>), g, b, 0, s, p);
-    else if (mode == 1) hipLaunchKernelGGL((scan_bytes_kernel<true, 1, false>), g, b, 0, s, p);
-    else if (live) hipLaunchKernelGGL((scan_bytes_kernel<true, 2, true>), g, b, 0, s, p);
-    else hipLaunchKernelGGL((scan_bytes_kernel<true, 2, false>), g, b, 0, s, p);
+    if (mode == 0) hipLaunchKernelGGL((scan_bytes_kernel<true, 0, false, kS0>), g, b, 0, s, p);
+    else if (mode == 1 && live) hipLaunchKernelGGL((scan_bytes_kernel<true, 1, true, kSx>), g, b, 0, s, p);
+    else if (mode == 1) hipLaunchKernelGGL((scan_bytes_kernel<true, 1, false, kSx>), g, b, 0, s, p);
+    else if (live) hipLaunchKernelGGL((scan_bytes_kernel<true, 2, true, kSx>), g, b, 0, s, p);
+    else hipLaunchKernelGGL((scan_bytes_kernel<true, 2, false, kSx>), g, b, 0, s, p);
     return hipGetLastError();
 }
 

@@ -20,7 +20,8 @@ import torch  # noqa: E402
 import blt_amd  # noqa: E402
 from blt_amd import synth  # noqa: E402
 
-TILE = 32768
+TILE = 32768   # the smallest byte-pass tile (sizes the record buffer); the records' strides follow the
+               # tile of the instantiation that ran (blt_debug_last_byte_tile)
 CHUNK = 16 << 20
 
 
@@ -50,6 +51,9 @@ def main():
         L.blt_debug_set_tile_record(dbg.data_ptr() if it == 2 else None)
         s.encode_device(d_in.data_ptr(), n, CHUNK, d_out.data_ptr(), ws.data_ptr(), wsb, sp, sync=True)
     L.blt_debug_set_tile_record(None)
+    tile = int(L.blt_debug_last_byte_tile()) if hasattr(L, "blt_debug_last_byte_tile") else TILE
+    ntiles = (n + tile - 1) // tile
+    print(f"tile {tile} bytes, {ntiles} tiles")
     rec = dbg.cpu().numpy().astype(np.int64)
     # workgroup start / table copied / exit (s_memrealtime, 100 MHz) against the tiles' publishes
     wg = rec[(8 + 8 * 16) * ntiles:].reshape(-1, 4)
