@@ -620,7 +620,7 @@ inline uint64_t up256(uint64_t x) { return (x + 255) & ~255ull; }
 
 struct WsLayout {
     uint64_t ntiles, nchunks;
-    uint64_t ctl, status, status2, total, off_a, off_b, cmap, cmap_stride, gstat, bytes, zero_bytes;
+    uint64_t ctl, status, status2, chain, off_a, off_b, cmap, cmap_stride, gstat, bytes, zero_bytes;
     // sparse passes of a cyclic map (run_sparse): bitmaps of n bits, seed and merge lists of
     // sp_cap entries, compaction tile words, counters; sp_cap 0 when the map cannot use them
     uint64_t sp_holes, sp_bits0, sp_bits1, sp_bits2, sp_seeds0, sp_seeds1, sp_merges, sp_tileo, sp_status, sp_ctr, sp_ntiles,
@@ -631,16 +631,20 @@ struct WsLayout {
 constexpr uint32_t kMaxBoundedPasses = 64;
 inline bool chain_bounded(const blt_bpe* h) { return h->chain_depth && h->chain_depth <= kMaxBoundedPasses + 1; }
 // Sparse passes per run_sparse call (one counter pair each, zeroed once; a longer tail goes back to
-// the full passes).  Counter words: [0] overflow flag, [1] unused, [2 + p] pass p's seeds,
-// [2 + kSparseMaxPasses + 1 + p] pass p's merges.
+// the full passes).  Counter words: the overflow flags, one unused, then pass p's seeds and pass
+// p's merges (kSparseMaxPasses + 1 of each: a pass also counts the seeds of the pass after it).
 constexpr uint32_t kSparseMaxPasses = 250;
 constexpr uint32_t kSparseCtrWords = 2 + 2 * (kSparseMaxPasses + 1);
-// Chain block of a general map (right after pass 1's status words): u64 pass totals [2], u32 done
-// word, u32 fused-fail word, u64 final total, u32 finish-gate word, pad.
-constexpr uint64_t kChainBlock = 48;
+constexpr uint32_t kSpCtrOverflow = 0;
+constexpr uint32_t sp_ctr_seeds(uint32_t p) { return 2 + p; }
+constexpr uint32_t sp_ctr_merges(uint32_t p) { return 2 + (kSparseMaxPasses + 1) + p; }
+static_assert(sp_ctr_seeds(kSparseMaxPasses) < sp_ctr_merges(0) && sp_ctr_merges(kSparseMaxPasses) < kSparseCtrWords,
+              "sparse counter words");
+// Bytes of the chain block the host reads back: the totals, the done and fused-fail words, the final total.
+constexpr size_t kChainRead = offsetof(blt::ChainBlock, fin_gate);
 
 // Workspace: control block and look-back status words (zeroed before each pass), then for a
-// general map the pass totals and done flag, two chunk-offset arrays (the passes alternate) and
+// general map the chain block (blt::ChainBlock), two chunk-offset arrays (the passes alternate) and
 // the chunk map of the u16 scan kernel (one word per kTokRange tokens).  The u16 passes run in
 // place in the caller's output.
 WsLayout ws_layout(const blt_bpe* h, uint64_t n, uint64_t cs) {
@@ -653,9 +657,9 @@ WsLayout ws_layout(const blt_bpe* h, uint64_t n, uint64_t cs) {
     L.ctl = 0;
     L.status = blt::kCtlBytes;
     L.zero_bytes = up16(blt::kCtlBytes + 8 * L.ntiles);
-    L.total = L.zero_bytes;   // the chain block (kChainBlock bytes, right after pass 1's status
-                              // words: encode_device zeroes both at once)
-    L.off_a = L.total + kChainBlock;
+    L.chain = L.zero_bytes;   // the chain block, right after pass 1's status words (a general map's
+                              // encode zeroes both at once); a single pass uses its first word, the total
+    L.off_a = L.chain + sizeof(blt::ChainBlock);
     L.off_b = L.off_a + up16(8 * (L.nchunks + 1));
     // three chunk maps: u16 scan pass k reads map k % 3, builds k + 1's and zeroes k + 2's (each on
     // cache lines of its own: one is zeroed while the next is marked)
@@ -679,7 +683,10 @@ WsLayout ws_layout(const blt_bpe* h, uint64_t n, uint64_t cs) {
         L.sp_seeds1 = L.sp_seeds0 + up16(4 * cap);
         L.sp_merges = L.sp_seeds1 + up16(4 * cap);
         L.sp_tileo = L.sp_merges + up16(12 * cap);
-        L.sp_status = L.sp_tileo + up16(4 * ((sptiles + 15) & ~15ull) + 16);
+        // the tile counts padded to 16 words, then the super_cnt words (run_sparse points super_cnt
+        // there).  This tail lies between sp_tileo and sp_ctr, so inside the range the first sparse
+        // kernel zeroes (SparseParams::zero16): the tickets start every run at zero.
+        L.sp_status = L.sp_tileo + up16(4 * ((sptiles + 15) & ~15ull) + 4 * blt::kSparseSuperWords);
         L.sp_ctr = L.sp_status + up16(8 * sptiles);
         // + the gate's sample, then the list slices' counts: seeds (two, alternating by pass), merges
         L.sp_slices = L.sp_ctr + up16(4ull * kSparseCtrWords) + 4ull * blt::kSparseSampleBlocks;
@@ -713,21 +720,56 @@ int check_ctl(uint8_t* ws, hipStream_t s) {
     return ctl_error(ctl);
 }
 
-// Enqueues one merge pass over n positions.
-// u16 passes of a general map: the token count comes from the device and is written there.
-struct Chain {
-    const uint64_t* n_in = nullptr;   // count written by the previous pass
-    uint64_t* n_out = nullptr;        // this pass's count
-    uint32_t* done = nullptr;         // set to its pass_id by the last pass that can merge anything
-    uint32_t pass_id = 0;             // 1, 2, ...
-    bool next_scan = false;           // the next pass runs on the scan kernel too (it builds its chunk map)
+// ---- pass runners ------------------------------------------------------------------------
+// What every runner of one encode shares: the handle, its tables on the device, the stream and the
+// workspace with its layout.
+struct EncodeCtx {
+    const blt_bpe* h;
+    const DevTables* t;
+    int dev;
+    hipStream_t s;
+    uint8_t* ws;
+    const WsLayout& L;
+    template <class T>
+    T* at(uint64_t off) const { return reinterpret_cast<T*>(ws + off); }
+    blt::ChainBlock* chain() const { return at<blt::ChainBlock>(L.chain); }   // (a device pointer)
 };
 
-// What the previous launch of a chain left for the next u16 pass (round 6).  Chained u16 passes
-// (scan or merge kernel) alternate two sets of look-back status words and ticket words; each pass
-// zeroes the other set for the pass after it, so only the first pass of a run needs the chunk-map
-// kernel (scan) or a memset (merge) to zero its own.  Any other kernel in between (the finish or
-// sparse kernels) resets it.
+// The fields blt::PassParams and blt::SparseParams share: the map's bucket table, the chunk count,
+// the control block, the handle's error word and the injection hook.
+template <class P>
+void fill_shared(const EncodeCtx& c, P* p) {
+    p->nchunks = c.L.nchunks;
+    p->ctl = c.at<uint32_t>(c.L.ctl);
+    p->hbuckets = c.t->hbuckets;
+    p->hmul1 = c.h->hmul1;
+    p->hmul2 = c.h->hmul2;
+    p->hshift = c.h->hshift;
+    p->hbytes = (uint32_t)(c.h->hwords.size() * sizeof(uint32_t));
+    p->hone = c.h->hone ? 1u : 0u;
+    p->sticky = c.h->sticky.load(std::memory_order_acquire);
+    p->inject = g_inject.load(std::memory_order_relaxed);
+}
+// What every PassParams user sets.
+blt::PassParams pass_params(const EncodeCtx& c) {
+    blt::PassParams p{};
+    fill_shared(c, &p);
+    p.debug = g_debug_tiles;
+    return p;
+}
+// The byte-pair table fields of the byte pass and the generic kernel (the u16 passes carry them too).
+void fill_dense(const EncodeCtx& c, blt::PassParams* p, const uint16_t* dense) {
+    p->sentinel = c.h->sentinel;
+    p->dense = dense;
+    p->allm = c.h->allmerge ? 1u : 0u;
+    p->mark = c.h->mark | (c.h->mark << 16);
+}
+
+// What the previous launch of a chain left for the next u16 pass.  Chained u16 passes (scan or
+// merge kernel) alternate two sets of look-back status words and ticket words; each pass zeroes the
+// other set for the pass after it, so only the first pass of a run needs the chunk-map kernel
+// (scan) or a memset (merge) to zero its own.  Any other kernel in between (the finish or sparse
+// kernels) resets it.
 struct U16Run {
     bool map_ready = false;   // the previous pass was a scan pass that built this pass's chunk map
     bool st_ready = false;    // the previous pass zeroed set `par`'s status words and ticket
@@ -735,134 +777,191 @@ struct U16Run {
     void reset() { map_ready = st_ready = false; }
 };
 
-// tok_scan: a u16 pass on the scan kernel (every chunk holds >= kTokRange tokens).  run (u16 passes
-// of a chain): see U16Run, updated for the next pass.
-int run_pass(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8_t* ws, const WsLayout& L,
-             const void* in, bool in_u16, uint64_t n, uint64_t cs, const uint64_t* cstart, void* out, bool be,
-             uint64_t out_cap, uint64_t* chunk_off, bool ws_zeroed = false, const Chain* chain = nullptr,
-             bool tok_scan = false, U16Run* run = nullptr) {
-    const bool columnar = !in_u16 && cs >= blt::kMinChunkBytes && h->byte_mode >= 0 && be;   // byte-pass fast kernel
+struct SparseRun {
+    bool gated = false;      // the chain had ended (or the fused kernel must fall back): nothing ran
+    bool taken = false;      // detect found few enough seeds: the passes ran
+    bool complete = false;   // ... to the fixpoint (else the full passes go on from the compaction)
+    uint32_t passes = 0;     // passes enqueued: the compaction wrote the total as pass k + passes - 1's
+    uint32_t applied = 0;    // passes that did work: up to the last with seeds, before any overflow
+    blt::ChainBlock rec{};   // the chain block's totals, done and fallback words, as read last
+    bool rec_final = false;  // ... read after the compaction
+};
+
+// Where a general map's chain stands.  u16 pass k reads the total tot[(k - 1) & 1] and writes
+// tot[k & 1]; the done word holds the pass after which nothing merges.  The chunk offsets alternate
+// between two arrays, and follow k too until a sparse run: its passes (any number) go through one
+// compaction, which writes the other array once.  So pass k reads off[((k - 1) & 1) ^ off_shift]
+// and writes the other, and a sparse run of an even number of passes flips off_shift.
+struct ChainPos {
+    blt::ChainBlock* cb;      // on the device
+    uint64_t* off[2];
+    uint64_t k = 1;           // the next u16 pass to enqueue
+    uint32_t off_shift = 0;
+    // passes enqueued that did nothing (a sparse run's passes after its fixpoint or its overflow):
+    // k counts them (the compaction wrote its total as the last enqueued pass's), the pass counts
+    // reported and checked do not
+    uint64_t k_idle = 0;
+    bool fin_tried = false;   // the finish kernels, once per encode
+    // sparse passes: tried once, right behind the byte pass or at a read of the pass counts; once
+    // more at a read of the pass counts when the try behind the byte pass found its lists too small
+    // (cyclic_dense: every word start a seed at first, a few long words at the end)
+    bool sp_tried = false, sp_retry = false;
+    U16Run u16;               // what the previous launch left for the next u16 pass (run_u16_pass)
+
+    const uint64_t* tot_in() const { return &cb->tot[(k - 1) & 1]; }
+    uint64_t* tot_out() const { return &cb->tot[k & 1]; }
+    uint32_t cur() const { return (uint32_t)((k - 1) & 1) ^ off_shift; }
+    const uint64_t* off_in() const { return off[cur()]; }
+    uint64_t* off_out() const { return off[cur() ^ 1u]; }
+    void passed() { ++k; }
+    void passed(const SparseRun& r) {
+        k += r.passes;
+        k_idle += r.passes - r.applied;
+        off_shift ^= (r.passes & 1u) ^ 1u;
+    }
+    uint64_t passes_done() const { return k - 1 - k_idle; }   // passes that did work
+    // the results of pass kd, the last enqueued or the done word's
+    uint64_t total_of(const blt::ChainBlock& rec, uint64_t kd) const { return rec.tot[kd & 1]; }
+    uint64_t* off_of(uint64_t kd) const { return off[(uint32_t)(kd & 1) ^ off_shift]; }
+    // the finish kernels, at the first u16 pass whose input chunks may fit in LDS
+    bool finish_now(uint64_t cs) {
+        if (fin_tried || k >= 64 || (cs >> k) > blt::kFinCapTokens) return false;
+        fin_tried = true;
+        return true;
+    }
+};
+
+// A pass over bytes: a merges file's single pass, or pass 1 of a general map's chain (pass id 0),
+// big-endian tokens out.  On the columnar kernel when the chunk size and the map allow, else on the
+// generic one.
+struct BytePass {
+    const uint8_t* in;
+    uint64_t n, cs;
+    uint8_t* out;          // 2 n bytes
+    uint64_t* chunk_off;
+    // pass 1 of a chain: the caller has zeroed the workspace with the chain block, and the pass
+    // marks itself final in the done word when it made no key component (byte-pair keys)
+    bool chain = false;
+    bool ws_zeroed = false;   // a single pass: the caller's BLT_ENCODE_WORKSPACE_ZEROED (no memset; the kernel checks)
+};
+int run_byte_pass(const EncodeCtx& c, const BytePass& a) {
+    const blt_bpe* h = c.h;
+    const bool columnar = a.cs >= blt::kMinChunkBytes && h->byte_mode >= 0;   // byte-pass fast kernel
     // the byte pass's tile is the picked instantiation's (48 KiB for merges files, else 32 KiB): this
     // line gives the launch its ntiles, and the kernel uses the first ntiles of the workspace's
     // ceil(n / kTilePosBytes) status words (ws_layout, blt_bpe_workspace_reset: 32 KiB units, unchanged)
-    const int byte_live = (chain && h->live_first) ? 1 : 0;
-    const uint64_t tile = columnar ? blt::scan_bytes_tile(h->byte_mode, byte_live)
-                                   : in_u16 ? (tok_scan ? blt::kTilePosTok : blt::kTilePosU16) : blt::kTilePos;
-    const uint64_t ntiles = (n + tile - 1) / tile;
+    const int byte_live = (a.chain && h->live_first) ? 1 : 0;
+    const uint64_t tile = columnar ? blt::scan_bytes_tile(h->byte_mode, byte_live) : blt::kTilePos;
+    const uint64_t ntiles = (a.n + tile - 1) / tile;
     if (ntiles > 0xFFFFFFFFull) return fail(BLT_E_INVALID_INPUT, "input too large");
-    if (!(g_u16_chain.load(std::memory_order_relaxed) & 1)) run = nullptr;
-    const bool chained = in_u16 && chain && run;
-    // (the u16 scan's chunk-map kernel zeroes the control block and status words itself, and a
-    // chained pass finds them zeroed by the pass before it)
-    const bool merge_ready = chained && !tok_scan && run->st_ready;
-    if (!ws_zeroed && !(in_u16 && tok_scan) && !merge_ready) {
-        HIP_TRY(hipMemsetAsync(ws, 0, up16(blt::kCtlBytes + 8 * ntiles), s));
-        if (chained) run->par = 0;   // (the memset zeroed set 0: the control block and pass 1's words)
-    }
-    blt::PassParams p{};
-    p.in = in;
-    p.n = n;
-    p.cs = cs;
-    p.cstart = cstart;
-    p.nchunks = L.nchunks;
-    p.out = out;
-    p.out_cap = out_cap;
-    p.chunk_off = chunk_off;
-    p.status = reinterpret_cast<uint64_t*>(ws + L.status);
-    p.ctl = reinterpret_cast<uint32_t*>(ws + L.ctl);
-    p.total = chain ? chain->n_out : reinterpret_cast<uint64_t*>(ws + L.total);
-    if (chain) {
-        p.n_dev = chain->n_in;
-        p.done = chain->done;
-        p.pass_id = chain->pass_id;
-    }
+    if (!a.chain && !a.ws_zeroed) HIP_TRY(hipMemsetAsync(c.ws, 0, up16(blt::kCtlBytes + 8 * ntiles), c.s));
+    blt::PassParams p = pass_params(c);
+    p.in = a.in;
+    p.n = a.n;
+    p.cs = a.cs;
+    p.out = a.out;
+    p.out_cap = 2 * a.n;
+    p.chunk_off = a.chunk_off;
+    p.status = c.at<uint64_t>(c.L.status);
+    p.total = &c.chain()->tot[0];
+    if (a.chain) p.done = &c.chain()->done;
     p.ntiles = (uint32_t)ntiles;
-    p.sentinel = h->sentinel;
-    p.dense = columnar ? (be ? t->self_be : t->self_ne) : t->dense;
-    p.hbuckets = t->hbuckets;
-    p.hmul1 = h->hmul1;
-    p.hmul2 = h->hmul2;
-    p.hshift = h->hshift;
-    p.hbytes = (uint32_t)(h->hwords.size() * sizeof(uint32_t));
-    p.hone = h->hone ? 1u : 0u;
-    p.cs_magic = cs ? ~0ull / cs : 0;
-    if (cs && cs % blt::kSubPosBytes == 0 && n / blt::kSubPosBytes < (1ull << 31) - 8) {
+    fill_dense(c, &p, columnar ? c.t->self_be : c.t->dense);
+    p.cs_magic = ~0ull / a.cs;
+    if (a.cs % blt::kSubPosBytes == 0 && a.n / blt::kSubPosBytes < (1ull << 31) - 8) {
         // 32-bit chunk geometry in sub-tile units: a tile's first sub-tile index (below 2^31, a
         // whole tile past the buffer's last included) divided by the chunk's sub-tiles
-        p.cs_subs = (uint32_t)std::min<uint64_t>(cs / blt::kSubPosBytes, 0x7FFFFFFFull);
+        p.cs_subs = (uint32_t)std::min<uint64_t>(a.cs / blt::kSubPosBytes, 0x7FFFFFFFull);
         p.cs_subs_magic = p.cs_subs > 1 ? (uint32_t)(0xFFFFFFFFull / p.cs_subs) : 0u;
     }
-    p.allm = h->allmerge ? 1u : 0u;
-    p.mark = h->mark | (h->mark << 16);
-    p.debug = g_debug_tiles;
-    p.inject = g_inject.load(std::memory_order_relaxed);
-    p.sticky = h->sticky.load(std::memory_order_acquire);
-    const bool scan16 = in_u16 && tok_scan;
-    const bool ready = scan16 && chained && run->map_ready;
-    auto map = [&](uint32_t i) { return reinterpret_cast<uint64_t*>(ws + L.cmap + (uint64_t)(i % 3u) * L.cmap_stride); };
-    const uint32_t r = chain ? chain->pass_id % 3u : 0u;
-    if (scan16) p.cmap = map(r);
+    p.ws_check = (!a.chain && a.ws_zeroed) ? 1u : 0u;
+    if (columnar) {
+        HIP_TRY(blt::launch_scan_bytes(p, h->byte_mode, byte_live, c.dev, c.s));
+        t_last_byte_tile = (uint32_t)tile;
+    } else HIP_TRY(blt::launch_merge_pass(p, /*input_u16=*/0, /*big_endian=*/1, c.dev, c.s));
+    return 0;
+}
+
+// u16 pass pos->k of a general map's chain, in place in tok (at most n tokens; the count comes from
+// the device, the previous pass's total, and this pass's is written there), then the chain moves on.
+struct U16Kernel {
+    bool scan;        // the scan kernel (every chunk holds >= kTokRange tokens), else the merge kernel
+    bool next_scan;   // the next pass runs on the scan kernel too (this one builds its chunk map)
+};
+int run_u16_pass(const EncodeCtx& c, uint8_t* tok, uint64_t n, const U16Kernel& a, ChainPos* pos) {
+    U16Run* run = &pos->u16;
+    const uint64_t tile = a.scan ? blt::kTilePosTok : blt::kTilePosU16;
+    const uint64_t ntiles = (n + tile - 1) / tile;
+    if (ntiles > 0xFFFFFFFFull) return fail(BLT_E_INVALID_INPUT, "input too large");
+    const bool chained = (g_u16_chain.load(std::memory_order_relaxed) & 1) != 0;
+    // (the scan's chunk-map kernel zeroes the control block and status words itself, and a chained
+    // pass finds them zeroed by the pass before it)
+    if (!a.scan && !(chained && run->st_ready)) {
+        HIP_TRY(hipMemsetAsync(c.ws, 0, up16(blt::kCtlBytes + 8 * ntiles), c.s));
+        if (chained) run->par = 0;   // (the memset zeroed set 0: the control block and pass 1's words)
+    }
+    blt::PassParams p = pass_params(c);
+    p.in = tok;
+    p.n = n;
+    p.cstart = pos->off_in();
+    p.out = tok;
+    p.out_cap = 2 * n;
+    p.chunk_off = pos->off_out();
+    p.status = c.at<uint64_t>(c.L.status);
+    p.total = pos->tot_out();
+    p.n_dev = pos->tot_in();
+    p.done = &pos->cb->done;
+    p.pass_id = (uint32_t)pos->k;
+    p.ntiles = (uint32_t)ntiles;
+    fill_dense(c, &p, c.t->dense);
+    const bool ready = a.scan && chained && run->map_ready;
+    auto map = [&](uint32_t i) { return c.at<uint64_t>(c.L.cmap + (uint64_t)(i % 3u) * c.L.cmap_stride); };
+    const uint32_t r = p.pass_id % 3u;
+    if (a.scan) p.cmap = map(r);
     if (chained) {
         // this pass's set of status words and ticket, zeroed by the pass before it (or by the
         // chunk-map kernel or the memset); the other set zeroed here for the next pass
         const bool alt = run->par != 0;
-        p.status = reinterpret_cast<uint64_t*>(ws + (alt ? L.status2 : L.status));
-        p.status_zero = reinterpret_cast<uint64_t*>(ws + (alt ? L.status : L.status2));
+        p.status = c.at<uint64_t>(alt ? c.L.status2 : c.L.status);
+        p.status_zero = c.at<uint64_t>(alt ? c.L.status : c.L.status2);
         p.tick = alt ? blt::kCtlTickAlt : 0u;
-        if (scan16 && chain->next_scan) {   // the next pass's chunk map, built here
+        if (a.scan && a.next_scan) {   // the next pass's chunk map, built here
             p.cmap_next = map(r + 1u);
             p.cmap_zero = map(r + 2u);
         }
         run->par ^= 1u;
         run->st_ready = true;
-        run->map_ready = scan16 && chain->next_scan;
+        run->map_ready = a.scan && a.next_scan;
     }
-    p.ws_check = (ws_zeroed && !in_u16 && !chain) ? 1u : 0u;   // the caller's BLT_ENCODE_WORKSPACE_ZEROED
-    if (columnar) {
-        HIP_TRY(blt::launch_scan_bytes(p, h->byte_mode, byte_live, dev, s));
-        t_last_byte_tile = (uint32_t)tile;
-    }
-    else if (scan16) {
-        HIP_TRY(blt::launch_scan_tokens(p, ready ? 1 : 0, dev, s));
+    if (a.scan) {
+        HIP_TRY(blt::launch_scan_tokens(p, ready ? 1 : 0, c.dev, c.s));
         ++t_last_scan_passes;
-    }
-    else HIP_TRY(blt::launch_merge_pass(p, in_u16 ? 1 : 0, be ? 1 : 0, dev, s));
+    } else HIP_TRY(blt::launch_merge_pass(p, /*input_u16=*/1, /*big_endian=*/1, c.dev, c.s));
+    pos->passed();
     return 0;
 }
 
 // Passes 1 and 2 of a general map in one launch (blt::launch_scan_fused): bytes d_in to the second
-// pass's tokens in d_out, its total, chunk offsets and done word as u16 pass 1's.
-int run_fused(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8_t* ws, const WsLayout& L,
-              const uint8_t* d_in, uint64_t n, uint64_t cs, uint8_t* d_out, uint64_t* chunk_off, uint64_t* total,
-              uint32_t* done, uint32_t* fused_fail) {
+// pass's tokens in d_out, its total, chunk offsets and done word as u16 pass 1's (pos->k = 1).
+int run_fused(const EncodeCtx& c, const uint8_t* d_in, uint64_t n, uint64_t cs, uint8_t* d_out, ChainPos* pos) {
     const uint64_t ntiles = (n + blt::kTilePosTok - 1) / blt::kTilePosTok;
     if (ntiles > 0xFFFFFFFFull) return fail(BLT_E_INVALID_INPUT, "input too large");
-    blt::PassParams p{};
+    blt::PassParams p = pass_params(c);
     p.in = d_in;
     p.n = n;
     p.cs = cs;
-    p.nchunks = L.nchunks;
     p.out = d_out;
     p.out_cap = 2 * n;
-    p.chunk_off = chunk_off;
-    p.status = reinterpret_cast<uint64_t*>(ws + L.status);
-    p.ctl = reinterpret_cast<uint32_t*>(ws + L.ctl);
-    p.total = total;
-    p.done = done;
-    p.pass_id = 1;
+    p.chunk_off = pos->off_out();
+    p.status = c.at<uint64_t>(c.L.status);
+    p.total = pos->tot_out();
+    p.done = &pos->cb->done;
+    p.pass_id = (uint32_t)pos->k;
     p.ntiles = (uint32_t)ntiles;
-    p.hbuckets = t->hbuckets;
-    p.hmul1 = h->hmul1;
-    p.hmul2 = h->hmul2;
-    p.hshift = h->hshift;
-    p.hbytes = (uint32_t)(h->hwords.size() * sizeof(uint32_t));
-    p.hone = h->hone ? 1u : 0u;
     p.cs_magic = ~0ull / cs;
-    p.debug = g_debug_tiles;
-    p.inject = g_inject.load(std::memory_order_relaxed);
-    p.sticky = h->sticky.load(std::memory_order_acquire);
-    p.fused_fail = fused_fail;
-    HIP_TRY(blt::launch_scan_fused(p, dev, s));
+    p.fused_fail = &pos->cb->fused_fail;
+    HIP_TRY(blt::launch_scan_fused(p, c.dev, c.s));
+    pos->passed();
     return 0;
 }
 
@@ -871,30 +970,19 @@ int run_fused(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint
 // total as pass k's.  Enqueued once per encode, at the first pass whose input chunks may fit in LDS
 // (a pass at least halves a chunk's tokens: they hold >= cs >> k entering u16 pass k); when a group
 // does not fit after all, the gate leaves it to the ordinary pass k enqueued right behind it.
-int run_finish(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8_t* ws, const WsLayout& L,
-               uint8_t* d_out, uint32_t k, const uint64_t* off_in, uint64_t* off_out, uint64_t* total, uint32_t* done) {
-    blt::PassParams p{};
+int run_finish(const EncodeCtx& c, uint8_t* d_out, ChainPos* pos) {
+    blt::PassParams p = pass_params(c);
     p.in = d_out;
     p.out = d_out;
-    p.cstart = off_in;
-    p.nchunks = L.nchunks;
-    p.chunk_off = off_out;
-    p.total = total;
-    p.done = done;
-    p.pass_id = k;
-    p.status = reinterpret_cast<uint64_t*>(ws + L.gstat);
-    p.ctl = reinterpret_cast<uint32_t*>(ws + L.ctl);
-    p.hbuckets = t->hbuckets;
-    p.hmul1 = h->hmul1;
-    p.hmul2 = h->hmul2;
-    p.hshift = h->hshift;
-    p.hbytes = (uint32_t)(h->hwords.size() * sizeof(uint32_t));
-    p.hone = h->hone ? 1u : 0u;
-    p.sticky = h->sticky.load(std::memory_order_acquire);
-    p.fin_gate = reinterpret_cast<uint32_t*>(ws + L.total + 32);
-    p.debug = g_debug_tiles;
-    p.inject = g_inject.load(std::memory_order_relaxed);
-    HIP_TRY(blt::launch_finish(p, dev, s));
+    p.cstart = pos->off_in();
+    p.chunk_off = pos->off_out();
+    p.total = pos->tot_out();
+    p.done = &pos->cb->done;
+    p.pass_id = (uint32_t)pos->k;
+    p.status = c.at<uint64_t>(c.L.gstat);
+    p.fin_gate = &pos->cb->fin_gate;
+    HIP_TRY(blt::launch_finish(p, c.dev, c.s));
+    pos->u16.reset();
     return 0;
 }
 
@@ -906,11 +994,11 @@ std::atomic<int> g_finish{1};
 // chunk-map kernel resets only the ticket); a generic u16 pass (merge_tokens_kernel, chunks under
 // kTokRange tokens) zeroes the whole control block before its launch, so an error flagged earlier in
 // the chain is reported by the sticky message alone.
-int chain_sticky(const blt_bpe* h, uint8_t* ws, const WsLayout& L, uint64_t passes) {
-    if (!sticky_check(h)) return 0;
+int chain_sticky(const EncodeCtx& c, uint64_t passes) {
+    if (!sticky_check(c.h)) return 0;
     const std::string sticky_msg = t_err;
     uint32_t ctl[16] = {0};
-    if (hipMemcpy(ctl, ws + L.ctl, sizeof ctl, hipMemcpyDeviceToHost) == hipSuccess && ctl_error(ctl))
+    if (hipMemcpy(ctl, c.ws + c.L.ctl, sizeof ctl, hipMemcpyDeviceToHost) == hipSuccess && ctl_error(ctl))
         return fail(BLT_E_IO, "%s; u16 passes 1..%llu: %s", sticky_msg.c_str(), (unsigned long long)passes, t_err.c_str());
     return fail(BLT_E_IO, "%s", sticky_msg.c_str());
 }
@@ -931,22 +1019,12 @@ thread_local uint32_t t_last_sparse = 0;
 // not-taken path.
 std::atomic<uint32_t> g_sparse_cap{0};
 
-struct SparseRun {
-    bool gated = false;      // the chain had ended (or the fused kernel must fall back): nothing ran
-    bool taken = false;      // detect found few enough seeds: the passes ran
-    bool complete = false;   // ... to the fixpoint (else the full passes go on from the compaction)
-    uint32_t passes = 0;     // passes enqueued: the compaction wrote the total as pass k + passes - 1's
-    uint32_t applied = 0;    // passes that did work: up to the last with seeds, before any overflow
-    uint64_t rec[4] = {0, 0, 0, 0};   // the chain block's totals, done and fallback words, as read last
-    bool rec_final = false;  // ... read after the compaction
-};
-
 // Host words of the sparse passes' reads (pinned: the reads sit between the device's launches),
 // from the handle's free list (blt_bpe::sp_free); a failed allocation leaves the sparse passes out
 // of that encode (the full passes give the same tokens).
 struct SparseHost {
     uint32_t ctr[kSparseCtrWords];
-    uint64_t rec[4];
+    blt::ChainBlock rec;
 };
 struct SparseHostLease {
     const blt_bpe* h;
@@ -969,61 +1047,52 @@ struct SparseHostLease {
     }
 };
 
-// After u16 pass k - 1 (its token count at n_dev on the device, at most n_max, in place in d_out;
-// chunk starts off_in): sparse passes k, k + 1, ... in the hole layout, then the compaction into
-// d_out, off_out and tot[(k + passes - 1) & 1], as the full passes would leave them.  Enqueued
-// without reading anything first: the detect kernel, four passes and the compaction (which runs only
-// when the four passes reached the fixpoint and detect's seeds fit the lists), then one read of the
-// counters and the chain block.  Passes went on past four: more batches, one read each, then the
-// compaction (the caller reads the totals).  Nothing changes when the gate word (done and fallback
-// words) is set or detect's seeds overflow the lists (not taken).
+// After u16 pass k - 1, k = pos.k (its token count on the device, at most n_max, in place in tok;
+// chunk starts pos.off_in()): sparse passes k, k + 1, ... in the hole layout, then the compaction
+// into tok, pos.off_out() and the chain block's tot[(k + passes - 1) & 1], as the full passes would
+// leave them.  Enqueued without reading anything first: the detect kernel, four passes and the compaction
+// (which runs only when the four passes reached the fixpoint and detect's seeds fit the lists), then
+// one read of the counters and the chain block.  Passes went on past four: more batches, one read
+// each, then the compaction (the caller reads the totals).  Nothing changes when the gate word (done
+// and fallback words) is set or detect's seeds overflow the lists (not taken).
 // Concurrent runs (threads sharing a handle, several handles, several processes on one device)
 // need no coordination: the two kernels whose workgroups wait for other workgroups
 // (sparse_list_kernel, sparse_move_kernel) take their work from tickets, so a workgroup only waits
-// for lower tickets, held by workgroups that have started (round 5 serialised the batches per
-// device with a lock and an event, because those kernels relied on blockIdx dispatch order).
-int run_sparse(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uint8_t* ws, const WsLayout& L,
-               uint8_t* d_out, const uint64_t* n_dev, uint64_t n_max, const uint64_t* gate, uint64_t k,
-               const uint64_t* off_in, uint64_t* off_out, uint64_t* tot, SparseRun* r) {
+// for lower tickets, held by workgroups that have started.
+int run_sparse(const EncodeCtx& c, uint8_t* tok, const ChainPos& pos, const uint64_t* gate, uint64_t n_max, SparseRun* r) {
+    const WsLayout& L = c.L;
+    const hipStream_t s = c.s;
     *r = SparseRun{};
-    SparseHostLease lease(h);
+    SparseHostLease lease(c.h);
     SparseHost* hb = lease.p;
     if (!L.sp_cap || !hb || n_max == 0 || n_max >= (1ull << 32)) return 0;
-    if (dev < 0 || dev >= kMaxDevices) return fail(BLT_E_NODEV, "device index %d out of range", dev);
-    uint32_t* ctr = reinterpret_cast<uint32_t*>(ws + L.sp_ctr);
+    if (c.dev < 0 || c.dev >= kMaxDevices) return fail(BLT_E_NODEV, "device index %d out of range", c.dev);
+    uint32_t* ctr = c.at<uint32_t>(L.sp_ctr);
+    uint64_t* tot = pos.cb->tot;
     blt::SparseParams q{};
-    q.tok = reinterpret_cast<uint16_t*>(d_out);
+    fill_shared(c, &q);
+    q.tok = reinterpret_cast<uint16_t*>(tok);
     q.n = n_max;
-    q.n_dev = n_dev;
+    q.n_dev = pos.tot_in();
     q.gate = gate;
-    q.holes = reinterpret_cast<uint32_t*>(ws + L.sp_holes);
-    q.flags = ctr;
-    q.merges = reinterpret_cast<uint32_t*>(ws + L.sp_merges);
+    q.holes = c.at<uint32_t>(L.sp_holes);
+    q.flags = ctr + kSpCtrOverflow;
+    q.merges = c.at<uint32_t>(L.sp_merges);
     const uint32_t cap_over = g_sparse_cap.load(std::memory_order_relaxed);
     q.cap = cap_over ? std::min(cap_over, L.sp_cap) : L.sp_cap;
-    q.hbuckets = t->hbuckets;
-    q.hmul1 = h->hmul1;
-    q.hmul2 = h->hmul2;
-    q.hshift = h->hshift;
-    q.hbytes = (uint32_t)(h->hwords.size() * sizeof(uint32_t));
-    q.hone = h->hone ? 1u : 0u;
-    q.coff_in = off_in;
-    q.coff_out = off_out;
-    q.nchunks = L.nchunks;
-    q.tile_cnt = reinterpret_cast<uint32_t*>(ws + L.sp_tileo);   // (8 B per tile: the counts padded to 16, the total)
+    q.coff_in = pos.off_in();
+    q.coff_out = pos.off_out();
+    q.tile_cnt = c.at<uint32_t>(L.sp_tileo);   // (8 B per tile: the counts padded to 16, the super_cnt words)
     q.super_cnt = q.tile_cnt + ((L.sp_ntiles + 15) & ~15ull);
-    q.status = reinterpret_cast<uint64_t*>(ws + L.sp_status);
-    // counters, tile counts and status words: zeroed by the first sparse kernel (a memset is one
-    // more launch, ~5 us; two when its size is not whole 16-byte units)
-    q.zero = reinterpret_cast<uint4*>(ws + L.sp_tileo);
+    q.status = c.at<uint64_t>(L.sp_status);
+    // counters, tile counts (with the super_cnt words) and status words: zeroed by the first sparse
+    // kernel (a memset is one more launch, ~5 us; two when its size is not whole 16-byte units)
+    q.zero = c.at<uint4>(L.sp_tileo);
     q.zero16 = (uint32_t)(((L.sp_ctr - L.sp_tileo) + up16(4ull * kSparseCtrWords)) / 16);
-    q.sample = reinterpret_cast<uint32_t*>(ws + L.sp_ctr + up16(4ull * kSparseCtrWords));
-    q.ctl = reinterpret_cast<uint32_t*>(ws + L.ctl);
-    q.sticky = h->sticky.load(std::memory_order_acquire);
-    q.inject = g_inject.load(std::memory_order_relaxed);
-    uint32_t* seeds[2] = {reinterpret_cast<uint32_t*>(ws + L.sp_seeds0), reinterpret_cast<uint32_t*>(ws + L.sp_seeds1)};
-    uint32_t* bits0 = reinterpret_cast<uint32_t*>(ws + L.sp_bits0);
-    uint32_t* bits[2] = {reinterpret_cast<uint32_t*>(ws + L.sp_bits1), reinterpret_cast<uint32_t*>(ws + L.sp_bits2)};
+    q.sample = c.at<uint32_t>(L.sp_ctr + up16(4ull * kSparseCtrWords));
+    uint32_t* seeds[2] = {c.at<uint32_t>(L.sp_seeds0), c.at<uint32_t>(L.sp_seeds1)};
+    uint32_t* bits0 = c.at<uint32_t>(L.sp_bits0);
+    uint32_t* bits[2] = {c.at<uint32_t>(L.sp_bits1), c.at<uint32_t>(L.sp_bits2)};
     // pass p reads list p & 1 (pass 0's from sparse_list_kernel); its seed bitmap is detect's bits0
     // for pass 0, then bits[(p - 1) & 1], which pass p - 1 wrote (and pass p's apply kernel clears)
     // list slices: one per wave of the region kernel, at least 256 entries each (small inputs run
@@ -1034,28 +1103,28 @@ int run_sparse(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uin
         q.nslices = nsl;
         q.slice = q.cap / nsl;
     }
-    uint32_t* cnts = reinterpret_cast<uint32_t*>(ws + L.sp_slices);
+    uint32_t* cnts = c.at<uint32_t>(L.sp_slices);
     q.cnt_merges = cnts + 2 * blt::kSparseSlices;
     auto at_pass = [&](uint32_t pp) {   // pass pp's lists and counters
         q.cnt_in = pp ? cnts + ((pp - 1) & 1) * blt::kSparseSlices : nullptr;
         q.cnt_seeds = cnts + (pp & 1) * blt::kSparseSlices;
         q.seeds_in = seeds[pp & 1];
         q.bits_in = pp ? bits[(pp - 1) & 1] : bits0;
-        q.nseeds_in = ctr + 2 + pp;
+        q.nseeds_in = ctr + sp_ctr_seeds(pp);
         q.seeds_out = seeds[(pp + 1) & 1];
         q.bits_out = bits[pp & 1];
         q.bits_alt = bits[1];
-        q.nseeds_out = ctr + 2 + pp + 1;
-        q.nmerges = ctr + 2 + (kSparseMaxPasses + 1) + pp;
+        q.nseeds_out = ctr + sp_ctr_seeds(pp + 1);
+        q.nmerges = ctr + sp_ctr_merges(pp);
         q.first_pass = pp == 0 ? 1u : 0u;
     };
-    const uint32_t* nseeds0 = ctr + 2;
+    const uint32_t* nseeds0 = ctr + sp_ctr_seeds(0);
     at_pass(0);
     HIP_TRY(blt::launch_sparse_detect(q, s));
-    {   // pass 0's list: bits0 into list 0, counter ctr[2]
+    {   // pass 0's list: bits0 into list 0, its count the seeds of pass 0
         blt::SparseParams ql = q;
         ql.seeds_out = seeds[0];
-        ql.nseeds_out = ctr + 2;
+        ql.nseeds_out = ctr + sp_ctr_seeds(0);
         HIP_TRY(blt::launch_sparse_list(ql, s));
     }
     constexpr uint32_t kFirst = 4;
@@ -1064,34 +1133,34 @@ int run_sparse(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uin
         at_pass(pp);
         HIP_TRY(blt::launch_sparse_pass(q, s));
     }
-    q.cond = ctr + 2 + kFirst;   // pass kFirst's seeds: none = the fixpoint
-    q.total = tot + ((k + kFirst - 1) & 1);
+    q.cond = ctr + sp_ctr_seeds(kFirst);   // pass kFirst's seeds: none = the fixpoint
+    q.total = tot + ((pos.k + kFirst - 1) & 1);
     HIP_TRY(blt::launch_sparse_compact(q, nseeds0, s));
-    uint32_t* c = hb->ctr;
+    const uint32_t* hc = hb->ctr;
     // passes that did work, of the pp enqueued: those before the first that overflowed a list (its
     // merges were dropped and every later region kernel returned at once), and of those the ones up
     // to the last that had seeds (a pass without seeds merges nothing)
     auto applied = [&](uint32_t npass) {
-        uint32_t a = 0;
+        uint32_t done = 0;
         for (uint32_t p = 0; p < npass; ++p) {
-            if (c[2 + (kSparseMaxPasses + 1) + p] > q.cap || c[2 + p + 1] > q.cap) break;
-            if (c[2 + p] == 0) break;
-            a = p + 1;
+            if (hc[sp_ctr_merges(p)] > q.cap || hc[sp_ctr_seeds(p + 1)] > q.cap) break;
+            if (hc[sp_ctr_seeds(p)] == 0) break;
+            done = p + 1;
         }
-        return a;
+        return done;
     };
-    HIP_TRY(hipMemcpyAsync(c, ctr, sizeof hb->ctr, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(hb->rec, tot, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(hb->ctr, ctr, sizeof hb->ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&hb->rec, pos.cb, kChainRead, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    std::copy(hb->rec, hb->rec + 4, r->rec);
-    if (r->rec[2]) {   // (the gate: done or fallback words)
+    r->rec = hb->rec;
+    if (r->rec.done || r->rec.fused_fail) {   // (the gate)
         r->gated = true;
         return 0;
     }
-    if (c[0] & 2u) return 0;   // not taken: the first pass overflowed the lists, nothing was applied
+    if (hc[kSpCtrOverflow] & 2u) return 0;   // not taken: the first pass overflowed the lists, nothing was applied
     r->taken = true;
-    bool overflow = c[0] != 0;
-    if (c[2 + kFirst] == 0) {   // the compaction ran
+    bool overflow = hc[kSpCtrOverflow] != 0;
+    if (hc[sp_ctr_seeds(kFirst)] == 0) {   // the compaction ran
         r->rec_final = true;
         r->passes = kFirst;
         r->applied = applied(kFirst);
@@ -1099,23 +1168,211 @@ int run_sparse(const blt_bpe* h, const DevTables* t, int dev, hipStream_t s, uin
         t_last_sparse = kFirst | (r->complete ? 1u << 16 : 0u) | (overflow ? 1u << 17 : 0u);
         return 0;
     }
-    while (!overflow && c[2 + pp] != 0 && pp < kSparseMaxPasses) {   // (the seeds of pass pp, the next to run)
+    while (!overflow && hc[sp_ctr_seeds(pp)] != 0 && pp < kSparseMaxPasses) {   // (pass pp is the next to run)
         const uint32_t e = std::min<uint32_t>(pp + 8, kSparseMaxPasses);
         for (; pp < e; ++pp) {
             at_pass(pp);
             HIP_TRY(blt::launch_sparse_pass(q, s));
         }
-        HIP_TRY(hipMemcpyAsync(c, ctr, sizeof hb->ctr, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(hb->ctr, ctr, sizeof hb->ctr, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        overflow = c[0] != 0;
+        overflow = hc[kSpCtrOverflow] != 0;
     }
     r->passes = pp;
     r->applied = applied(pp);
-    r->complete = !overflow && c[2 + pp] == 0;
+    r->complete = !overflow && hc[sp_ctr_seeds(pp)] == 0;
     q.cond = nullptr;
-    q.total = tot + ((k + pp - 1) & 1);
+    q.total = tot + ((pos.k + pp - 1) & 1);
     HIP_TRY(blt::launch_sparse_compact(q, nseeds0, s));
     t_last_sparse = pp | (r->complete ? 1u << 16 : 0u) | (overflow ? 1u << 17 : 0u);
+    return 0;
+}
+
+// ---- encode: a single pass, a bounded chain, an open chain ----------------------------------
+struct EncodeCall {   // blt_bpe_encode_device's arguments
+    const uint8_t* d_in;
+    uint64_t n, cs;
+    uint8_t* d_out;
+    uint64_t* d_chunk_off;
+    void* d_ws;
+    size_t ws_bytes;
+    uint64_t* out_tokens;
+    uint32_t flags;
+};
+// What an encode step returns besides 0 (the encode has ended) and an error: the chain goes on.
+constexpr int kGoOn = 1;
+
+int encode_single(const EncodeCtx& c, const EncodeCall& a) {
+    BytePass bp{a.d_in, a.n, a.cs, a.d_out, a.d_chunk_off};
+    bp.ws_zeroed = (a.flags & BLT_ENCODE_WORKSPACE_ZEROED) != 0;
+    if (int rc = run_byte_pass(c, bp)) return rc;
+    if (!a.out_tokens) return 0;
+    if (int rc = read_u64(&c.chain()->tot[0], a.out_tokens, c.s)) return rc;
+    return check_ctl(c.ws, c.s);
+}
+
+// A wave range the fused kernel could not resolve: the two-kernel chain from the start (below).
+int fused_fallback(const EncodeCtx& c, const EncodeCall& a);
+
+// The start of a general map's chain: the memset, then the fused passes 1 + 2 or the byte pass.
+int chain_start(const EncodeCtx& c, const EncodeCall& a, bool fused, ChainPos* pos) {
+    // pass 1's control block and status words and the chain block are contiguous: one memset
+    // (BLT_ENCODE_WORKSPACE_ZEROED is ignored here, as the header says)
+    HIP_TRY(hipMemsetAsync(c.ws, 0, c.L.zero_bytes + sizeof(blt::ChainBlock), c.s));
+    if (!fused) {   // pass 1 (pass id 0): with byte-pair keys it marks itself final when it made no key component
+        BytePass bp{a.d_in, a.n, a.cs, a.d_out, pos->off[0]};
+        bp.chain = true;
+        const int rc = run_byte_pass(c, bp);
+        return rc ? rc : kGoOn;
+    }
+    if (int rc = run_fused(c, a.d_in, a.n, a.cs, a.d_out, pos)) return rc;
+    if (g_fused_only.load(std::memory_order_relaxed) && a.out_tokens) {   // (test hook)
+        uint32_t ff = 0;
+        HIP_TRY(hipMemcpyAsync(&ff, &pos->cb->fused_fail, sizeof ff, hipMemcpyDeviceToHost, c.s));
+        if (int rc = read_u64(&pos->cb->tot[1], a.out_tokens, c.s)) return rc;
+        t_last_fused = ff ? 2 : 1;   // 2: a halo without a restart, the output is not defined
+        return 0;
+    }
+    if (chain_bounded(c.h) && c.h->chain_depth > 2) {
+        // more passes to enqueue: see first whether the fused kernel resolved every range (a
+        // failed one leaves them no-ops, but each costs its launch)
+        uint32_t ff = 0;
+        HIP_TRY(hipMemcpyAsync(&ff, &pos->cb->fused_fail, sizeof ff, hipMemcpyDeviceToHost, c.s));
+        HIP_TRY(hipStreamSynchronize(c.s));
+        if (int rc = chain_sticky(c, 1)) return rc;
+        if (ff) return fused_fallback(c, a);
+    }
+    return kGoOn;
+}
+
+// A bounded chain (no value can be made from itself): u16 passes 1 .. depth - 1 are all a pass can
+// need, enqueued without reading the device's pass count; passes after the one that marks the
+// fixpoint return at once, and a last kernel picks the final pass's total and chunk offsets.  Only
+// a caller asking for the token count waits (once).
+int encode_bounded(const EncodeCtx& c, const EncodeCall& a, bool fused, ChainPos* pos) {
+    const uint32_t k_last = c.h->chain_depth - 1;
+    auto scan_ok = [&](uint64_t kk) { return kk < 64 && (a.cs >> kk) >= blt::kTokRange; };
+    while (pos->k <= k_last) {
+        if (pos->finish_now(a.cs)) {
+            if (int rc = run_finish(c, a.d_out, pos)) return rc;
+            if (a.out_tokens) {
+                // a caller that waits anyway: see whether the finish ran (its gate word, the longest
+                // chunk, fit in LDS) before enqueueing the passes it turned into no-ops
+                uint32_t lmax = 0;
+                HIP_TRY(hipMemcpyAsync(&lmax, &pos->cb->fin_gate, sizeof lmax, hipMemcpyDeviceToHost, c.s));
+                HIP_TRY(hipStreamSynchronize(c.s));
+                if (lmax <= blt::kFinCapTokens) break;
+            }
+        }
+        const U16Kernel on{scan_ok(pos->k), pos->k + 1 <= k_last && scan_ok(pos->k + 1)};
+        if (int rc = run_u16_pass(c, a.d_out, a.n, on, pos)) return rc;
+    }
+    HIP_TRY(blt::launch_chain_final(pos->cb->tot, &pos->cb->done, pos->off[1], a.d_chunk_off, c.L.nchunks, k_last,
+                                    &pos->cb->tot_final, c.s));
+    if (!a.out_tokens) return 0;
+    blt::ChainBlock rec{};
+    HIP_TRY(hipMemcpyAsync(&rec, pos->cb, kChainRead, hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    if (int rc = chain_sticky(c, k_last)) return rc;
+    if (fused && rec.fused_fail) return fused_fallback(c, a);
+    t_last_u16_passes = rec.done ? (rec.done & ~blt::kDoneBytePass) : k_last;
+    *a.out_tokens = rec.tot_final;
+    return 0;
+}
+
+// One try of the sparse passes behind pass k - 1, whose count (at most n_max) the device holds: a
+// run that was taken moves the chain past the passes it ran, to the compaction's results, and may
+// end the encode (0).  gate: the chain block's done | fused-fail word for a try enqueued without
+// reading them (behind the byte pass; lists found too small there earn one more try), else null.
+int try_sparse(const EncodeCtx& c, const EncodeCall& a, ChainPos* pos, const uint64_t* gate, uint64_t n_max) {
+    pos->sp_tried = true;
+    SparseRun r;
+    if (int rc = run_sparse(c, a.d_out, *pos, gate, n_max, &r)) return rc;
+    pos->u16.reset();
+    pos->sp_retry = gate && !r.taken && !r.gated;
+    if (!r.taken) return kGoOn;
+    pos->passed(r);
+    if (!r.rec_final) {   // (the totals to read)
+        HIP_TRY(hipMemcpyAsync(&r.rec, pos->cb, kChainRead, hipMemcpyDeviceToHost, c.s));
+        HIP_TRY(hipStreamSynchronize(c.s));
+    }
+    if (int rc = chain_sticky(c, pos->passes_done())) return rc;
+    if (!r.complete) return kGoOn;
+    t_last_u16_passes = (uint32_t)pos->passes_done();
+    if (a.d_chunk_off && pos->off_of(pos->k - 1) != a.d_chunk_off)
+        HIP_TRY(hipMemcpyAsync(a.d_chunk_off, pos->off_of(pos->k - 1), 8 * (c.L.nchunks + 1), hipMemcpyDeviceToDevice, c.s));
+    if (a.out_tokens) *a.out_tokens = pos->total_of(r.rec, pos->k - 1);
+    return 0;
+}
+
+// An open-ended or cyclic chain: the host enqueues a batch of passes at a time and reads the pass
+// totals and the done word once per batch (passes after the done one return at once).  The scan
+// kernel also ends the chain after a pass none of whose merges made a key component, so most maps
+// finish after one u16 pass: the first batch is 1 pass, later ones 4.
+int encode_open(const EncodeCtx& c, const EncodeCall& a, bool fused, ChainPos* pos) {
+    const WsLayout& L = c.L;
+    t_last_sparse = 0;
+    if (!pos->sp_tried && !c.h->live_first) {   // (no fused kernel: see encode_device)
+        const int rc = try_sparse(c, a, pos, reinterpret_cast<const uint64_t*>(&pos->cb->done), a.n);
+        if (rc != kGoOn) return rc;
+    }
+    // A lower bound of the chunks' token counts (the last chunk's aside) beyond cs >> k: min_in for
+    // the input of pass min_k, read from the chunk offsets at a batch end; a pass at most halves a
+    // chunk.  It keeps the scan kernel on chunks that stay long (cyclic_dense: one letter per word
+    // and pass, 16 MiB chunks of ~9 M tokens) past the pass where cs >> k falls below kTokRange, in
+    // place of merge_tokens_kernel at twice the time per pass.  (The scan still checks: two chunk
+    // starts or ends in one wave range flag error bit 16.)
+    uint64_t min_in = 0, min_k = 0;
+    std::vector<uint64_t> hoff;
+    const int u16c = g_u16_chain.load(std::memory_order_relaxed);
+    auto scan_ok = [&](uint64_t kk) {
+        if (kk >= 64) return false;
+        if ((a.cs >> kk) >= blt::kTokRange) return true;
+        if (!(u16c & 2)) return false;
+        return min_in && kk >= min_k && kk - min_k < 64 && (min_in >> (kk - min_k)) >= blt::kTokRange;
+    };
+    blt::ChainBlock rec{};
+    for (int batch = 1;; batch = 4) {
+        for (int b = 0; b < batch; ++b) {
+            if (pos->finish_now(a.cs))
+                if (int rc = run_finish(c, a.d_out, pos)) return rc;
+            if (int rc = run_u16_pass(c, a.d_out, a.n, {scan_ok(pos->k), scan_ok(pos->k + 1)}, pos)) return rc;
+        }
+        const uint64_t k = pos->k;
+        HIP_TRY(hipMemcpyAsync(&rec, pos->cb, kChainRead, hipMemcpyDeviceToHost, c.s));
+        // the chunk offsets too when the next batch would leave the scan kernel by cs >> k alone
+        // (a few chunks: one more small copy in the same wait)
+        const bool rd_off = !scan_ok(k + 4) && L.nchunks >= 2 && L.nchunks <= 4096;
+        if (rd_off) {
+            hoff.resize(L.nchunks + 1);
+            HIP_TRY(hipMemcpyAsync(hoff.data(), pos->off_in(), 8 * (L.nchunks + 1), hipMemcpyDeviceToHost, c.s));
+        }
+        HIP_TRY(hipStreamSynchronize(c.s));
+        if (int rc = chain_sticky(c, pos->passes_done())) return rc;
+        if (fused && rec.fused_fail) return fused_fallback(c, a);
+        if (rec.done) break;
+        if (rd_off) {   // pass k's input chunks, the last aside
+            uint64_t m = ~0ull;
+            for (uint64_t i = 0; i + 1 < L.nchunks; ++i) m = std::min(m, hoff[i + 1] >= hoff[i] ? hoff[i + 1] - hoff[i] : 0);
+            min_in = m;
+            min_k = k;
+        }
+        if (k - pos->k_idle > a.n + 8)
+            return fail(BLT_E_IO, "general map: no fixpoint after %llu passes", (unsigned long long)(k - pos->k_idle));
+        // the last pass k - 1 left N tokens out of Nin (Nin unknown after the fused passes): the sparse
+        // passes are tried once that pass merged under 1/16 of its tokens.  (Under half of what the
+        // lists hold, a batch earlier on cyclic_dense, measured slower: 2.35 -> 3.50-3.57 ms.)
+        const uint64_t N = rec.tot[(k - 1) & 1], Nin = (k >= 3 || !fused) ? rec.tot[k & 1] : 0;
+        if ((!pos->sp_tried || pos->sp_retry) && Nin >= N && (Nin - N) * 16 < N) {
+            const int rc = try_sparse(c, a, pos, nullptr, N);
+            if (rc != kGoOn) return rc;
+        }
+    }
+    const uint32_t kdone = rec.done & ~blt::kDoneBytePass;   // 0: pass 1 was final
+    t_last_u16_passes = (uint32_t)(kdone ? kdone - pos->k_idle : 0);
+    if (a.d_chunk_off && pos->off_of(kdone) != a.d_chunk_off)
+        HIP_TRY(hipMemcpyAsync(a.d_chunk_off, pos->off_of(kdone), 8 * (L.nchunks + 1), hipMemcpyDeviceToDevice, c.s));
+    if (a.out_tokens) *a.out_tokens = pos->total_of(rec, kdone);
     return 0;
 }
 
@@ -1139,37 +1396,17 @@ int encode_device(const blt_bpe* h, const uint8_t* d_in, uint64_t n, uint64_t cs
     if (int rc = sticky_check(h)) return rc;
     DevTables* t;
     if (int rc = device_tables(h, dev, &t)) return rc;
-    uint8_t* ws = static_cast<uint8_t*>(d_ws);
-
-    if (h->single_pass) {
-        if (int rc = run_pass(h, t, dev, s, ws, L, d_in, false, n, cs, nullptr, d_out, true, 2 * n, d_chunk_off,
-                              (flags & BLT_ENCODE_WORKSPACE_ZEROED) != 0))
-            return rc;
-        if (out_tokens) {
-            if (int rc = read_u64(ws + L.total, out_tokens, s)) return rc;
-            return check_ctl(ws, s);
-        }
-        return 0;
-    }
+    const EncodeCtx c{h, t, dev, s, static_cast<uint8_t*>(d_ws), L};
+    const EncodeCall a{d_in, n, cs, d_out, d_chunk_off, d_ws, ws_bytes, out_tokens, flags};
+    if (h->single_pass) return encode_single(c, a);
 
     // General map: pass 1 on bytes into d_out, then passes on big-endian u16 tokens, in place in
     // d_out, until one merges nothing (tokenizer.rs:63-86; a pass that merges nothing leaves the
-    // tokens, so running it for every chunk once the slowest chunk is done changes nothing).  The
-    // chunk offsets alternate between two arrays.  The host enqueues a batch of passes at a time and
-    // reads the pass totals and the done flag once per batch (passes after the done one return at
-    // once).  u16 pass k runs on the scan kernel while every chunk holds >= kTokRange tokens
-    // (a pass at most halves a chunk: chunk_size >> k), else on the generic kernel.  The scan
-    // kernel also ends the chain after a pass none of whose merges made a key component, so
-    // most maps finish after one u16 pass: the first batch is 1 pass, later ones 4.  The done
-    // word holds the pass k after which nothing merges; its totals and chunk offsets are [k & 1].
+    // tokens, so running it for every chunk once the slowest chunk is done changes nothing).  u16
+    // pass k runs on the scan kernel while every chunk holds >= kTokRange tokens (a pass at most
+    // halves a chunk: chunk_size >> k), else on the generic kernel.
     if (L.nchunks >= (1ull << 32)) return fail(BLT_E_INVALID_INPUT, "too many chunks");
-    uint64_t* off[2] = {d_chunk_off ? d_chunk_off : reinterpret_cast<uint64_t*>(ws + L.off_a),
-                        reinterpret_cast<uint64_t*>(ws + L.off_b)};
-    uint64_t* tot = reinterpret_cast<uint64_t*>(ws + L.total);
-    uint32_t* done = reinterpret_cast<uint32_t*>(ws + L.total + 16);
-    // pass 1's control block and status words and the chain's totals are contiguous: one memset
-    // (BLT_ENCODE_WORKSPACE_ZEROED is ignored here, as the header says)
-    HIP_TRY(hipMemsetAsync(ws, 0, L.zero_bytes + kChainBlock, s));
+    ChainPos pos{c.chain(), {d_chunk_off ? d_chunk_off : c.at<uint64_t>(L.off_a), c.at<uint64_t>(L.off_b)}};
     t_last_scan_passes = 0;
     const bool bounded = chain_bounded(h);
     // Passes 1 and 2 in one kernel (run_fused) when the bucket table fits in LDS, chunks hold whole
@@ -1183,224 +1420,18 @@ int encode_device(const blt_bpe* h, const uint8_t* d_in, uint64_t n, uint64_t cs
                        !sp_on && !h->byte_self_pair &&
                        h->hwords.size() * sizeof(uint32_t) <= blt::kHashLdsMax && cs >= blt::kMinChunkBytes &&
                        (!bounded || out_tokens != nullptr);
-    uint32_t* fused_fail = reinterpret_cast<uint32_t*>(ws + L.total + 20);   // beside the done word
-    int cur = 0;
-    uint64_t k = 1;   // u16 passes enqueued
-    if (fused) {
-        if (int rc = run_fused(h, t, dev, s, ws, L, d_in, n, cs, d_out, off[1], tot + 1, done, fused_fail)) return rc;
-        cur = 1;
-        k = 2;
-        if (g_fused_only.load(std::memory_order_relaxed) && out_tokens) {   // (test hook)
-            uint32_t ff = 0;
-            HIP_TRY(hipMemcpyAsync(&ff, fused_fail, sizeof ff, hipMemcpyDeviceToHost, s));
-            if (int rc = read_u64(tot + 1, out_tokens, s)) return rc;
-            t_last_fused = ff ? 2 : 1;   // 2: a halo without a restart, the output is not defined
-            return 0;
-        }
-        if (bounded && h->chain_depth > 2) {
-            // more passes to enqueue: see first whether the fused kernel resolved every range (a
-            // failed one leaves them no-ops, but each costs its launch)
-            uint32_t ff = 0;
-            HIP_TRY(hipMemcpyAsync(&ff, fused_fail, sizeof ff, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (int rc = chain_sticky(h, ws, L, 1)) return rc;
-            if (ff) {
-                const int rc = encode_device(h, d_in, n, cs, d_out, d_chunk_off, d_ws, ws_bytes, s, out_tokens,
-                                             flags | kEncodeNoFused);
-                t_last_fused = 2;
-                return rc;
-            }
-        }
-    } else {   // pass 1 (pass id 0): with byte-pair keys it marks itself final when it made no key component
-        const Chain c0{nullptr, tot, done, 0};
-        if (int rc = run_pass(h, t, dev, s, ws, L, d_in, false, n, cs, nullptr, d_out, true, 2 * n, off[0], true, &c0))
-            return rc;
-    }
-    // a wave range the fused kernel could not resolve: the two-kernel chain from the start
-    auto fallback = [&]() {
-        const int rc = encode_device(h, d_in, n, cs, d_out, d_chunk_off, d_ws, ws_bytes, s, out_tokens, flags | kEncodeNoFused);
-        t_last_fused = 2;
-        return rc;
-    };
+    const int rc = chain_start(c, a, fused, &pos);
+    if (rc != kGoOn) return rc;
     t_last_fused = fused ? 1 : 0;
-    uint64_t rec[4] = {0, 0, 0, 0};
-    // what the previous launch left for the next u16 pass (run_pass)
-    U16Run u16run;
-    // the finish kernels, once per encode: at the first u16 pass whose input chunks may fit in LDS
-    bool fin_tried = !g_finish.load(std::memory_order_relaxed);
-    auto finish_now = [&](uint64_t kk) {
-        if (fin_tried || kk >= 64 || (cs >> kk) > blt::kFinCapTokens) return false;
-        fin_tried = true;
-        return true;
-    };
-    if (bounded) {
-        // a bounded chain (no value can be made from itself): u16 passes 1 .. depth - 1 are all a
-        // pass can need, enqueued without reading the device's pass count; passes after the one
-        // that marks the fixpoint return at once, and a last kernel picks the final pass's total
-        // and chunk offsets.  Only a caller asking for the token count waits (once).
-        const uint32_t k_last = h->chain_depth - 1;
-        for (; k <= k_last; ++k) {
-            const Chain c{tot + ((k - 1) & 1), tot + (k & 1), done, (uint32_t)k,
-                          k + 1 <= k_last && k + 1 < 64 && (cs >> (k + 1)) >= blt::kTokRange};
-            if (finish_now(k)) {
-                if (int rc = run_finish(h, t, dev, s, ws, L, d_out, (uint32_t)k, off[cur], off[cur ^ 1], tot + (k & 1), done))
-                    return rc;
-                u16run.reset();
-                if (out_tokens) {
-                    // a caller that waits anyway: see whether the finish ran (its gate word, the longest
-                    // chunk, fit in LDS) before enqueueing the passes it turned into no-ops
-                    uint32_t lmax = 0;
-                    HIP_TRY(hipMemcpyAsync(&lmax, ws + L.total + 32, sizeof lmax, hipMemcpyDeviceToHost, s));
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if (lmax <= blt::kFinCapTokens) break;
-                }
-            }
-            const bool scan = k < 64 && (cs >> k) >= blt::kTokRange;
-            if (int rc = run_pass(h, t, dev, s, ws, L, d_out, true, n, 0, off[cur], d_out, true, 2 * n, off[cur ^ 1],
-                                  false, &c, scan, &u16run))
-                return rc;
-            cur ^= 1;
-        }
-        uint64_t* tot_final = tot + 3;   // the chain block's last word
-        HIP_TRY(blt::launch_chain_final(tot, done, off[1], d_chunk_off, L.nchunks, k_last, tot_final, s));
-        if (!out_tokens) return 0;
-        HIP_TRY(hipMemcpyAsync(rec, tot, 32, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (int rc = chain_sticky(h, ws, L, k_last)) return rc;
-        if (fused && (rec[2] >> 32)) return fallback();
-        const uint32_t kd = (uint32_t)rec[2];
-        t_last_u16_passes = kd ? (kd & ~blt::kDoneBytePass) : k_last;
-        *out_tokens = rec[3];
-        return 0;
-    }
-    // sparse passes: tried once, right behind the byte pass or at a read of the pass counts; once
-    // more at a read of the pass counts when the try behind the byte pass found its lists too small
-    // (cyclic_dense: every word start a seed at first, a few long words at the end)
-    bool sp_tried = !sp_on, sp_retry = false;
-    t_last_sparse = 0;
-    // Before pass k the chain's arrays follow k: its input total is tot[(k - 1) & 1] and it writes
-    // tot[k & 1].  The chunk offsets follow cur, which a sparse run flips once whatever number of
-    // passes it ran: pass k reads off[cur] = off[((k - 1) & 1) ^ off_shift] and writes the other.
-    uint32_t off_shift = 0;
-    // passes enqueued that did nothing (a sparse run's passes after its fixpoint or its overflow):
-    // k counts them (the compaction wrote its total as the last enqueued pass's), the pass counts
-    // reported and checked do not
-    uint64_t k_idle = 0;
-    // a sparse run that was taken: the passes it ran, then the compaction's results, or the end
-    auto sparse_taken = [&](const SparseRun& r, bool* finished) -> int {
-        *finished = false;
-        cur ^= 1;
-        k += r.passes;
-        k_idle += r.passes - r.applied;
-        off_shift = (uint32_t)cur ^ (uint32_t)((k - 1) & 1);
-        if (!r.rec_final) {   // (the totals to read)
-            HIP_TRY(hipMemcpyAsync(rec, tot, 32, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        } else {
-            std::copy(r.rec, r.rec + 4, rec);
-        }
-        if (int rc = chain_sticky(h, ws, L, k - 1 - k_idle)) return rc;
-        if (!r.complete) return 0;
-        *finished = true;
-        t_last_u16_passes = (uint32_t)(k - 1 - k_idle);
-        if (d_chunk_off && off[cur] != d_chunk_off)
-            HIP_TRY(hipMemcpyAsync(d_chunk_off, off[cur], 8 * (L.nchunks + 1), hipMemcpyDeviceToDevice, s));
-        if (out_tokens) *out_tokens = rec[(k - 1) & 1];
-        return 0;
-    };
-    if (sp_on && !bounded && !h->live_first) {   // (no fused kernel: see fused above)
-        sp_tried = true;
-        SparseRun r;
-        const uint64_t* gate = reinterpret_cast<const uint64_t*>(done);   // done word | fallback word
-        if (int rc = run_sparse(h, t, dev, s, ws, L, d_out, tot + ((k - 1) & 1), n, gate, k, off[cur], off[cur ^ 1],
-                                tot, &r))
-            return rc;
-        u16run.reset();
-        if (r.taken) {
-            bool fin = false;
-            if (int rc = sparse_taken(r, &fin)) return rc;
-            if (fin) return 0;
-        } else if (!r.gated) {
-            sp_retry = true;
-        }
-    }
-    // A lower bound of the chunks' token counts (the last chunk's aside) beyond cs >> k: min_in for
-    // the input of pass min_k, read from the chunk offsets at a batch end; a pass at most halves a
-    // chunk.  It keeps the scan kernel on chunks that stay long (cyclic_dense: one letter per word
-    // and pass, 16 MiB chunks of ~9 M tokens) past the pass where cs >> k falls below kTokRange, in
-    // place of merge_tokens_kernel at twice the time per pass.  (The scan still checks: two chunk
-    // starts or ends in one wave range flag error bit 16.)
-    uint64_t min_in = 0, min_k = 0;
-    std::vector<uint64_t> hoff;
-    const int u16c = g_u16_chain.load(std::memory_order_relaxed);
-    auto scan_ok = [&](uint64_t kk) {
-        if (kk >= 64) return false;
-        if ((cs >> kk) >= blt::kTokRange) return true;
-        if (!(u16c & 2)) return false;
-        return min_in && kk >= min_k && kk - min_k < 64 && (min_in >> (kk - min_k)) >= blt::kTokRange;
-    };
-    for (int batch = 1;; batch = 4) {
-        for (int b = 0; b < batch; ++b, ++k) {
-            const Chain c{tot + ((k - 1) & 1), tot + (k & 1), done, (uint32_t)k, scan_ok(k + 1)};
-            if (finish_now(k)) {
-                if (int rc = run_finish(h, t, dev, s, ws, L, d_out, (uint32_t)k, off[cur], off[cur ^ 1], tot + (k & 1), done))
-                    return rc;
-                u16run.reset();
-            }
-            const bool scan = scan_ok(k);
-            if (int rc = run_pass(h, t, dev, s, ws, L, d_out, true, n, 0, off[cur], d_out, true, 2 * n, off[cur ^ 1],
-                                  false, &c, scan, &u16run))
-                return rc;
-            cur ^= 1;
-        }
-        HIP_TRY(hipMemcpyAsync(rec, tot, 32, hipMemcpyDeviceToHost, s));
-        // the chunk offsets too when the next batch would leave the scan kernel by cs >> k alone
-        // (a few chunks: one more small copy in the same wait)
-        const bool rd_off = !scan_ok(k + 4) && L.nchunks >= 2 && L.nchunks <= 4096;
-        if (rd_off) {
-            hoff.resize(L.nchunks + 1);
-            HIP_TRY(hipMemcpyAsync(hoff.data(), off[cur], 8 * (L.nchunks + 1), hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-        if (int rc = chain_sticky(h, ws, L, k - 1 - k_idle)) return rc;
-        if (fused && (rec[2] >> 32)) return fallback();
-        if ((uint32_t)rec[2]) break;
-        if (rd_off) {   // pass k's input chunks, the last aside
-            uint64_t m = ~0ull;
-            for (uint64_t c = 0; c + 1 < L.nchunks; ++c) m = std::min(m, hoff[c + 1] >= hoff[c] ? hoff[c + 1] - hoff[c] : 0);
-            min_in = m;
-            min_k = k;
-        }
-        if (k - k_idle > n + 8)
-            return fail(BLT_E_IO, "general map: no fixpoint after %llu passes", (unsigned long long)(k - k_idle));
-        // the last pass k - 1 left N tokens out of Nin (Nin unknown after the fused passes): the sparse
-        // passes are tried once that pass merged under 1/16 of its tokens.  (Under half of what the
-        // lists hold, a batch earlier on cyclic_dense, measured slower: 2.35 -> 3.50-3.57 ms.)
-        const uint64_t N = rec[(k - 1) & 1], Nin = (k >= 3 || !fused) ? rec[k & 1] : 0;
-        if ((!sp_tried || sp_retry) && Nin >= N && (Nin - N) * 16 < N) {
-            sp_tried = true;
-            sp_retry = false;
-            SparseRun r;
-            if (int rc = run_sparse(h, t, dev, s, ws, L, d_out, tot + ((k - 1) & 1), N, nullptr, k, off[cur],
-                                    off[cur ^ 1], tot, &r))
-                return rc;
-            u16run.reset();
-            if (r.taken) {
-                bool fin = false;
-                if (int rc = sparse_taken(r, &fin)) return rc;
-                if (fin) return 0;
-            }
-        }
-    }
-    const uint32_t kdone = (uint32_t)rec[2] & ~blt::kDoneBytePass;   // 0: pass 1 was final
-    t_last_u16_passes = (uint32_t)(kdone ? kdone - k_idle : 0);
-    const uint32_t last = kdone & 1u;              // the total the final pass wrote
-    const uint32_t olast = last ^ off_shift;       // and its chunk offsets (not off[last]
-                                                   // after a sparse run of an even number of passes)
-    if (d_chunk_off && off[olast] != d_chunk_off)
-        HIP_TRY(hipMemcpyAsync(d_chunk_off, off[olast], 8 * (L.nchunks + 1), hipMemcpyDeviceToDevice, s));
-    if (out_tokens) *out_tokens = rec[last];
-    return 0;
+    pos.fin_tried = !g_finish.load(std::memory_order_relaxed);
+    pos.sp_tried = !sp_on;
+    return bounded ? encode_bounded(c, a, fused, &pos) : encode_open(c, a, fused, &pos);
+}
+int fused_fallback(const EncodeCtx& c, const EncodeCall& a) {
+    const int rc = encode_device(c.h, a.d_in, a.n, a.cs, a.d_out, a.d_chunk_off, a.d_ws, a.ws_bytes, c.s, a.out_tokens,
+                                 a.flags | kEncodeNoFused);
+    t_last_fused = 2;
+    return rc;
 }
 
 // ---- per-device staging contexts for the host-buffer API ---------------------------------
@@ -1672,7 +1703,7 @@ int encode_host_multi(const blt_bpe* h, const std::vector<int>& devs, const uint
                 rc = fail(BLT_E_IO, "host-to-device copy failed on device %d", c->device);
             } else if (h->single_pass) {
                 rc = encode_device(h, P.d_in, len, cs, P.d_out, P.d_off, P.d_ws, P.ws_bytes, P.stream, nullptr);
-                if (!rc && (hipMemcpyAsync(P.h_rec, P.d_ws + L.total, 8, hipMemcpyDeviceToHost, P.stream) != hipSuccess ||
+                if (!rc && (hipMemcpyAsync(P.h_rec, P.d_ws + L.chain + offsetof(blt::ChainBlock, tot), 8, hipMemcpyDeviceToHost, P.stream) != hipSuccess ||
                             hipMemcpyAsync(P.h_rec + 1, P.d_ws + L.ctl, 64, hipMemcpyDeviceToHost, P.stream) != hipSuccess))
                     rc = fail(BLT_E_IO, "record copy failed on device %d", c->device);
             } else {

@@ -1,6 +1,7 @@
 // Internal interface between the host library (blt_host.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace blt {
@@ -83,6 +84,26 @@ struct PassParams {
                                // the iteration start, after the first and second barrier; spins
     uint32_t inject;           // test hook (kInject*): a count broken on purpose, 0 in production
 };
+// Chain block of a general map, in the workspace right after pass 1's status words (the host
+// zeroes both with one memset).  The kernels take pointers to its words (PassParams::total, n_dev,
+// done, fused_fail, fin_gate, SparseParams::gate); the host reads it back whole, or its first 32 bytes.
+struct ChainBlock {
+    uint64_t tot[2];       // token totals: u16 pass k reads tot[(k - 1) & 1] and writes tot[k & 1] (the
+                           // byte pass writes tot[0]; so does a single pass, the only word it uses)
+    uint32_t done;         // k: u16 pass k was final; kDoneBytePass: the byte pass was; 0: not yet
+    uint32_t fused_fail;   // the fused kernel met a halo without a restart (the host falls back)
+    uint64_t tot_final;    // a bounded chain's final total (chain_final_kernel)
+    uint32_t fin_gate;     // the longest chunk entering the finish kernel (capped; finish_gate_kernel)
+    uint32_t pad[3];
+};
+static_assert(sizeof(ChainBlock) == 48, "the chain block is 48 bytes of the workspace layout");
+static_assert(offsetof(ChainBlock, done) == 16 && offsetof(ChainBlock, fused_fail) == 20 &&
+                  offsetof(ChainBlock, tot_final) == 24 && offsetof(ChainBlock, fin_gate) == 32,
+              "chain block layout");
+// the sparse kernels' gate (SparseParams::gate) reads the done and fused-fail words as one u64
+static_assert(offsetof(ChainBlock, done) % 8 == 0 && offsetof(ChainBlock, fused_fail) == offsetof(ChainBlock, done) + 4,
+              "done and fused_fail form one aligned 8-byte word");
+
 // Test hook (blt_debug_set_inject): a kernel breaks one of its counts on purpose, to show that its
 // invariant checks turn the count into a flagged error (BLT_E_IO) and no store lands outside the
 // range the count should have given.  Finish kernel: the first pass's count; u16 scan: a tile's
@@ -171,7 +192,9 @@ struct SparseParams {
     uint64_t nchunks;
     uint64_t* total;            // tokens after compaction (may be the word n_dev points to: written last)
     uint32_t* tile_cnt;         // per compaction tile: holes in it (apply kernels), then holes before it (scan)
-    uint32_t* super_cnt;        // one word: the holes in all (scan)
+    uint32_t* super_cnt;        // kSparseSuperWords words behind tile_cnt: [kSpHolesTotal] the holes in all
+                                // (scan), [kSpListTicket] and [kSpMoveTicket] the list and move kernels'
+                                // work tickets (zeroed with the run's counters)
     uint64_t* status;           // per compaction tile: the list kernel's seed counts, then the move's
                                 // read marks (zeroed)
     uint32_t* ctl;              // the chain's control block (error flags)
@@ -183,6 +206,11 @@ struct SparseParams {
     uint32_t inject;            // test hook (kInjectSparseMove), 0 in production
 };
 constexpr uint64_t kSparseTile = 8192;    // positions per compaction tile
+// Words of SparseParams::super_cnt, the tail the workspace reserves behind tile_cnt.
+constexpr uint32_t kSpHolesTotal = 0, kSpListTicket = 1, kSpMoveTicket = 2;
+constexpr uint32_t kSparseSuperWords = 4;
+static_assert(kSpHolesTotal < kSparseSuperWords && kSpListTicket < kSparseSuperWords && kSpMoveTicket < kSparseSuperWords,
+              "the tail behind tile_cnt holds every super_cnt word");
 // Region / apply kernels: 256-thread workgroups, one list slice per wave (at most kSparseSlices)
 constexpr uint32_t kSparseSlices = 4096;
 // Positions the detect gate samples: kSparseSampleBlocks evenly spaced runs of 8192 positions.

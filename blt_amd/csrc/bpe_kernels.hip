@@ -3188,75 +3188,56 @@ __global__ void inject_error_kernel(uint32_t* ctl, uint32_t* sticky) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------
-// Persistent-grid size of a kernel on a device: CUs x resident workgroups per CU, queried once
-// per (device, kernel) and cached in atomics (launchers run concurrently from many host threads).
-struct GridCache {
-    std::atomic<int> cus[64];
-    std::atomic<int> occ[64][16];
+// Persistent-grid size of a kernel on a device: CUs x resident workgroups per CU, queried once per
+// (device, kernel function, dynamic LDS bytes of the query).  The cache is a list that only grows
+// at its head: launchers run concurrently from many host threads and a lookup takes no lock (two
+// threads that miss at once both query and both push; the entries are equal).  A process sees a
+// handful of entries: a kernel's LDS bytes follow the map's table size, a power of two.
+using PassKernel = void (*)(PassParams);
+struct GridEntry {
+    int device;
+    PassKernel fn;
+    size_t smem;
+    long long wgs;
+    const GridEntry* next;
 };
-static GridCache g_grid;   // zero-initialised (static storage)
-static int grid_for(uint32_t ntiles, int device, const void* fn, int threads, int kernel_id) {
-    int cus = 0, occ = 0;
-    if (device >= 0 && device < 64) {
-        cus = g_grid.cus[device].load(std::memory_order_relaxed);
-        occ = g_grid.occ[device][kernel_id].load(std::memory_order_relaxed);
-    }
-    if (!cus) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 1;
-        if (device >= 0 && device < 64) g_grid.cus[device].store(cus, std::memory_order_relaxed);
-    }
-    if (!occ) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, 0) != hipSuccess || occ < 1) occ = 1;
-        if (device >= 0 && device < 64) g_grid.occ[device][kernel_id].store(occ, std::memory_order_relaxed);
-    }
-    long long g = (long long)cus * occ;
-    if (g > (long long)ntiles) g = ntiles;
-    return (int)(g < 1 ? 1 : g);
-}
-
-// The same for a kernel whose occupancy depends on its dynamic LDS (the u16 pass with the map's
-// bucket table in LDS): cached per (device, kernel, bytes), so a chain of passes queries once.
-static std::mutex g_grid_mu;
-static std::unordered_map<uint64_t, int> g_grid_smem;
-static int grid_for_smem(uint32_t ntiles, int device, const void* fn, int threads, size_t smem) {
-    const uint64_t key = ((uint64_t)(uint32_t)device << 40) ^ ((uint64_t)(uintptr_t)fn << 20) ^ (uint64_t)smem;
-    int g = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_grid_mu);
-        auto it = g_grid_smem.find(key);
-        if (it != g_grid_smem.end()) g = it->second;
-    }
-    if (!g) {
+static std::atomic<const GridEntry*> g_grids{nullptr};
+static int grid_for(uint64_t ntiles, int device, PassKernel fn, int threads, size_t smem) {
+    long long wgs = 0;
+    for (const GridEntry* e = g_grids.load(std::memory_order_acquire); e && !wgs; e = e->next)
+        if (e->device == device && e->fn == fn && e->smem == smem) wgs = e->wgs;
+    if (!wgs) {
         int cus = 0, occ = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, smem) != hipSuccess || occ < 1) occ = 1;
-        g = cus * occ;
-        std::lock_guard<std::mutex> lk(g_grid_mu);
-        g_grid_smem[key] = g;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)fn, threads, smem) != hipSuccess || occ < 1) occ = 1;
+        wgs = (long long)cus * occ;
+        GridEntry* e = new GridEntry{device, fn, smem, wgs, g_grids.load(std::memory_order_relaxed)};
+        while (!g_grids.compare_exchange_weak(e->next, e, std::memory_order_release, std::memory_order_relaxed)) {}
     }
-    if ((uint64_t)g > ntiles) g = (int)ntiles;
-    return g < 1 ? 1 : g;
+    if ((uint64_t)wgs > ntiles) wgs = (long long)ntiles;
+    return (int)(wgs < 1 ? 1 : wgs);
+}
+
+// Launches the picked instantiation of a kernel that takes its PassParams by value.
+static hipError_t launch_pass(PassKernel fn, int grid, int threads, size_t smem, hipStream_t s, const PassParams& p) {
+    void* args[] = {const_cast<PassParams*>(&p)};
+    (void)hipLaunchKernel((const void*)fn, dim3((unsigned)grid), dim3((unsigned)threads), args, smem, s);
+    return hipGetLastError();
 }
 
 hipError_t launch_merge_pass(const PassParams& p, int input_u16, int big_endian, int device, hipStream_t s) {
     if (p.ntiles == 0) return hipSuccess;
     if (!input_u16) {
-        const void* fn = big_endian ? (const void*)merge_pass_kernel<uint8_t, true> : (const void*)merge_pass_kernel<uint8_t, false>;
-        const int grid = grid_for(p.ntiles, device, fn, kThreads, big_endian ? 1 : 0);
-        if (big_endian) hipLaunchKernelGGL((merge_pass_kernel<uint8_t, true>), dim3(grid), dim3(kThreads), 0, s, p);
-        else hipLaunchKernelGGL((merge_pass_kernel<uint8_t, false>), dim3(grid), dim3(kThreads), 0, s, p);
-        return hipGetLastError();
+        const PassKernel fn = big_endian ? merge_pass_kernel<uint8_t, true> : merge_pass_kernel<uint8_t, false>;
+        return launch_pass(fn, grid_for(p.ntiles, device, fn, kThreads, 0), kThreads, 0, s, p);
     }
     // u16 passes: big-endian in and out; the bucket table in LDS when it fits (then several
     // workgroups share a CU and cover each other's barriers).  p.ntiles is the upper bound the
     // input size allows; the kernel reads the actual count from p.n_dev.
     const bool lds = p.hbytes <= kHashLdsMax;
-    const void* fn = lds ? (const void*)merge_tokens_kernel<true> : (const void*)merge_tokens_kernel<false>;
+    const PassKernel fn = lds ? merge_tokens_kernel<true> : merge_tokens_kernel<false>;
     const size_t smem = lds ? p.hbytes : 0;
-    const int grid = grid_for_smem(p.ntiles, device, fn, kThreads, smem);
-    if (lds) hipLaunchKernelGGL((merge_tokens_kernel<true>), dim3((unsigned)grid), dim3(kThreads), smem, s, p);
-    else hipLaunchKernelGGL((merge_tokens_kernel<false>), dim3((unsigned)grid), dim3(kThreads), 0, s, p);
-    return hipGetLastError();
+    return launch_pass(fn, grid_for(p.ntiles, device, fn, kThreads, smem), kThreads, smem, s, p);
 }
 
 hipError_t launch_scan_bytes(const PassParams& p, int mode, int live, int device, hipStream_t s) {
@@ -3266,51 +3247,35 @@ hipError_t launch_scan_bytes(const PassParams& p, int mode, int live, int device
     constexpr int kS0 = scan_bytes_subtiles(0, 0), kSx = seg::kS;   // the instantiated geometries
     if (scan_bytes_subtiles(mode, live) != (mode == 0 ? kS0 : kSx)) return hipErrorInvalidValue;
     if (p.ntiles != (p.n + scan_bytes_tile(mode, live) - 1) / scan_bytes_tile(mode, live)) return hipErrorInvalidValue;
-    const void* fn = mode == 0 ? (const void*)scan_bytes_kernel<true, 0, false, kS0>
-                     : mode == 1 ? (live ? (const void*)scan_bytes_kernel<true, 1, true, kSx> : (const void*)scan_bytes_kernel<true, 1, false, kSx>)
-                                 : (live ? (const void*)scan_bytes_kernel<true, 2, true, kSx> : (const void*)scan_bytes_kernel<true, 2, false, kSx>);
-    // every byte-pass instantiation holds the whole LDS: one workgroup per CU, one cache entry
-    const int grid = grid_for(p.ntiles, device, fn, seg::kThreads, 4);
-    const dim3 g((unsigned)grid), b(seg::kThreads);
-    if (mode == 0) hipLaunchKernelGGL((scan_bytes_kernel<true, 0, false, kS0>), g, b, 0, s, p);
-    else if (mode == 1 && live) hipLaunchKernelGGL((scan_bytes_kernel<true, 1, true, kSx>), g, b, 0, s, p);
-    else if (mode == 1) hipLaunchKernelGGL((scan_bytes_kernel<true, 1, false, kSx>), g, b, 0, s, p);
-    else if (live) hipLaunchKernelGGL((scan_bytes_kernel<true, 2, true, kSx>), g, b, 0, s, p);
-    else hipLaunchKernelGGL((scan_bytes_kernel<true, 2, false, kSx>), g, b, 0, s, p);
-    return hipGetLastError();
+    // (every byte-pass instantiation holds the whole LDS: one workgroup per CU)
+    PassKernel fn = scan_bytes_kernel<true, 0, false, kS0>;
+    if (mode == 1) fn = live ? scan_bytes_kernel<true, 1, true, kSx> : scan_bytes_kernel<true, 1, false, kSx>;
+    if (mode == 2) fn = live ? scan_bytes_kernel<true, 2, true, kSx> : scan_bytes_kernel<true, 2, false, kSx>;
+    return launch_pass(fn, grid_for(p.ntiles, device, fn, seg::kThreads, 0), seg::kThreads, 0, s, p);
 }
 
+// The u16 scan kernels' grids are sized by their static LDS alone (the occupancy query is given no
+// dynamic LDS, the launch is): more workgroups than are resident at once take tiles by ticket in
+// turn.  Sizing them by the table too is a tuning change, to be measured on its own.
 hipError_t launch_scan_tokens(const PassParams& p, int map_ready, int device, hipStream_t s) {
     if (p.n == 0) return hipSuccess;
     // p.n bounds the token count the kernels read from p.n_dev
     const uint64_t ranges = (p.n + kTokRange - 1) / kTokRange;
     if (!map_ready) hipLaunchKernelGGL(seg::chunk_map_kernel, dim3((unsigned)((ranges + 255) / 256)), dim3(256), 0, s, p);
     const bool lds = p.hbytes <= kHashLdsMax;
-    const int mode = lds ? (p.hone ? 2 : 1) : 0;
-    const void* fn = mode == 2 ? (const void*)seg::scan_tokens_kernel<2>
-                     : mode == 1 ? (const void*)seg::scan_tokens_kernel<1> : (const void*)seg::scan_tokens_kernel<0>;
+    const PassKernel fn = !lds ? seg::scan_tokens_kernel<0> : p.hone ? seg::scan_tokens_kernel<2> : seg::scan_tokens_kernel<1>;
     const uint32_t ntiles = (uint32_t)((p.n + kTilePosTok - 1) / kTilePosTok);
-    const int grid = grid_for(ntiles, device, fn, seg::kThreads, 5 + mode);
     const size_t smem = lds ? ((size_t)p.hbytes + 1023) & ~(size_t)1023 : 0;   // whole KiB (LDS-DMA rows)
-    const dim3 g((unsigned)grid), b(seg::kThreads);
-    if (mode == 2) hipLaunchKernelGGL((seg::scan_tokens_kernel<2>), g, b, smem, s, p);
-    else if (mode == 1) hipLaunchKernelGGL((seg::scan_tokens_kernel<1>), g, b, smem, s, p);
-    else hipLaunchKernelGGL((seg::scan_tokens_kernel<0>), g, b, 0, s, p);
-    return hipGetLastError();
+    return launch_pass(fn, grid_for(ntiles, device, fn, seg::kThreads, 0), seg::kThreads, smem, s, p);
 }
 
 hipError_t launch_scan_fused(const PassParams& p, int device, hipStream_t s) {
     if (p.n == 0) return hipSuccess;
     if (p.hbytes > kHashLdsMax || p.cs < kMinChunkBytes || !p.fused_fail) return hipErrorInvalidValue;
-    const int mode = p.hone ? 2 : 1;
-    const void* fn = mode == 2 ? (const void*)seg::scan_tokens_kernel<2, true> : (const void*)seg::scan_tokens_kernel<1, true>;
+    const PassKernel fn = p.hone ? seg::scan_tokens_kernel<2, true> : seg::scan_tokens_kernel<1, true>;
     const uint32_t ntiles = (uint32_t)((p.n + kTilePosTok - 1) / kTilePosTok);
-    const int grid = grid_for(ntiles, device, fn, seg::kThreads, 8 + mode);
     const size_t smem = ((size_t)p.hbytes + 1023) & ~(size_t)1023;
-    const dim3 g((unsigned)grid), b(seg::kThreads);
-    if (mode == 2) hipLaunchKernelGGL((seg::scan_tokens_kernel<2, true>), g, b, smem, s, p);
-    else hipLaunchKernelGGL((seg::scan_tokens_kernel<1, true>), g, b, smem, s, p);
-    return hipGetLastError();
+    return launch_pass(fn, grid_for(ntiles, device, fn, seg::kThreads, 0), seg::kThreads, smem, s, p);
 }
 
 hipError_t launch_basic_expand(const uint8_t* in, uint64_t n, uint8_t* out, hipStream_t s) {
@@ -3334,17 +3299,10 @@ hipError_t launch_finish(const PassParams& p, int device, hipStream_t s) {
     if (p.nchunks == 0 || !p.fin_gate || p.nchunks > 0xFFFFFFFFull * 256u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(finish_gate_kernel, dim3((unsigned)((p.nchunks + 255) / 256)), dim3(256), 0, s, p);
     const bool lds = p.hbytes <= kHashLdsMax;
-    const int mode = lds ? (p.hone ? 2 : 1) : 0;
+    const PassKernel fn = !lds ? finish_chunks_kernel<0> : p.hone ? finish_chunks_kernel<2> : finish_chunks_kernel<1>;
     const size_t smem = lds ? (size_t)p.hbytes : 0;
     // persistent: one workgroup per CU (its LDS), no more than there are chunks
-    const void* fn = mode == 2 ? (const void*)finish_chunks_kernel<2>
-                     : mode == 1 ? (const void*)finish_chunks_kernel<1> : (const void*)finish_chunks_kernel<0>;
-    const int grid = grid_for_smem((uint32_t)std::min<uint64_t>(p.nchunks, 0xFFFFFFFFull), device, fn, kFinThreads, smem);
-    const dim3 g((unsigned)grid), b(kFinThreads);
-    if (mode == 2) hipLaunchKernelGGL((finish_chunks_kernel<2>), g, b, smem, s, p);
-    else if (mode == 1) hipLaunchKernelGGL((finish_chunks_kernel<1>), g, b, smem, s, p);
-    else hipLaunchKernelGGL((finish_chunks_kernel<0>), g, b, 0, s, p);
-    return hipGetLastError();
+    return launch_pass(fn, grid_for(p.nchunks, device, fn, kFinThreads, smem), kFinThreads, smem, s, p);
 }
 
 // ===========================================================================================
@@ -3583,7 +3541,7 @@ __global__ __launch_bounds__(256) void sparse_list_kernel(SparseParams qa) {
     // order workgroups are dispatched in; at most kListBlocks atomics).
     if (tid == 0) {
         s_bad = *qa.flags & 2u;
-        s_b = s_bad ? 0u : atomicAdd(qa.super_cnt + 1, 1u);   // (zeroed with the run's counters)
+        s_b = s_bad ? 0u : atomicAdd(qa.super_cnt + kSpListTicket, 1u);   // (zeroed with the run's counters)
     }
     __syncthreads();
     if (s_bad) return;
@@ -3924,7 +3882,7 @@ __global__ __launch_bounds__(1024) void sparse_tile_scan_kernel(SparseParams qa,
         if (tid == 0) s_carry += tot;
         __syncthreads();
     }
-    if (tid == 0) *q.super_cnt = s_carry;
+    if (tid == 0) q.super_cnt[kSpHolesTotal] = s_carry;
 }
 
 // A workgroup is two halves of kCpThreads threads; each half takes two consecutive tiles and loads
@@ -3947,7 +3905,7 @@ void sparse_move_kernel(SparseParams qa, const uint32_t* nseeds0) {
     const int half = (int)threadIdx.x / kCpThreads;
     const int tid = (int)threadIdx.x % kCpThreads, lane = tid & 63, wave = tid >> 6;
     const uint64_t n = *qa.n_dev, ntiles = (n + kSparseTile - 1) / kSparseTile;
-    if (threadIdx.x == 0) s_tk = atomicAdd(qa.super_cnt + 2, 1u);   // (zeroed with the run's counters)
+    if (threadIdx.x == 0) s_tk = atomicAdd(qa.super_cnt + kSpMoveTicket, 1u);   // (zeroed with the run's counters)
     __syncthreads();
     const uint64_t G0 = (uint64_t)s_tk * kMoveGroup;
     if (G0 >= ntiles) return;   // (uniform: the grid is sized for the host's count, >= the device's)
@@ -3989,7 +3947,7 @@ void sparse_move_kernel(SparseParams qa, const uint32_t* nseeds0) {
         const bool here = T < ntiles;   // (uniform per half; the halves keep step at every barrier)
         const uint64_t tile0 = T * kSparseTile;
         const uint32_t hb = here ? qa.tile_cnt[T] : 0u;   // holes before the tile (sparse_tile_scan_kernel)
-        const uint32_t hnext = !here ? 0u : T + 1 < ntiles ? qa.tile_cnt[T + 1] : *qa.super_cnt;
+        const uint32_t hnext = !here ? 0u : T + 1 < ntiles ? qa.tile_cnt[T + 1] : qa.super_cnt[kSpHolesTotal];
         const uint64_t O = tile0 - hb;
         const uint32_t e = (uint32_t)(O & 7u);
         uint32_t cnt[4], incl[4];
@@ -4077,7 +4035,7 @@ __global__ __launch_bounds__(64) void sparse_coff_kernel(SparseParams q, const u
     const int lane = threadIdx.x;
     if (c >= q.nchunks || sp_compact_skip(q, nseeds0)) return;
     if (c == 0 && lane == 0) {
-        const uint64_t total = *q.n_dev - *q.super_cnt;
+        const uint64_t total = *q.n_dev - q.super_cnt[kSpHolesTotal];
         *q.total = total;
         q.coff_out[q.nchunks] = total;
     }

@@ -229,3 +229,60 @@ def test_workspace_size_of_cyclic_maps():
     assert cyclic.workspace_size(big, cs) == bounded.workspace_size(big, cs)
     for x in (bounded, cyclic, single):
         x.close()
+
+
+# blt_bpe_workspace_size per handle: rows n, columns chunk_size (below).  Recorded with this loop from
+# the library as built before the chain block and the sparse words got names (the layout is ABI: a
+# caller's allocation of an older size must stay large enough, and nothing here should grow unnoticed).
+_WS_N = (1, 1023, 32768, 32769, 49153, 1 << 20, (1 << 32) - 1, 1 << 32)
+_WS_CS = (1, 1000, 4096, 1 << 20)
+_WS_BYTES = {
+    "single": (
+        (256, 256, 256, 256),
+        (16640, 256, 256, 256),
+        (524544, 768, 512, 256),
+        (524544, 768, 512, 256),
+        (786688, 1024, 512, 256),
+        (16777728, 17408, 4608, 512),
+        (68720525568, 69768448, 17826048, 1114368),
+        (68720525568, 69768448, 17826048, 1114368),
+    ),
+    "bounded": (
+        (1296, 1296, 1296, 1296),
+        (25616, 1296, 1296, 1296),
+        (787472, 2064, 1552, 1296),
+        (788496, 2832, 2320, 2064),
+        (1181712, 3088, 2320, 2064),
+        (25191168, 50688, 31488, 25600),
+        (103181975808, 205840128, 127926528, 102859008),
+        (103181975808, 205840128, 127926528, 102859008),
+    ),
+    "cyclic": (
+        (134800, 134800, 134800, 134800),
+        (160848, 136528, 136528, 136528),
+        (978272, 192864, 192352, 192096),
+        (979376, 193712, 193200, 192944),
+        (1401280, 222656, 221888, 221632),
+        (27161072, 2020592, 2001392, 1995504),
+        (110704593392, 7728457712, 7650544112, 7625476592),
+        (103181975808, 205840128, 127926528, 102859008),
+    ),
+}
+
+
+def test_workspace_size_is_pinned(tmp_path):
+    """Host-only: blt_bpe_workspace_size of a merges-file single pass, a bounded general map and a
+    cyclic general map, byte for byte."""
+    from blt_amd import synth
+    path = tmp_path / "merges.txt"
+    path.write_text(synth.merges_file_text([(97, 98), (101, 32)]))
+    handles = {"single": blt_amd.BpeStrategy.from_file(str(path)),
+               "bounded": blt_amd.BpeStrategy(synth.CHAINED_TEXT_MAP),
+               "cyclic": blt_amd.BpeStrategy(synth.SELF_VALUED_MAP)}
+    L = _lib.lib()
+    assert L.blt_debug_chain_depth(handles["single"].handle) == 0
+    assert L.blt_debug_chain_depth(handles["bounded"].handle) == 2
+    for name, s in handles.items():
+        got = tuple(tuple(s.workspace_size(n, cs) for cs in _WS_CS) for n in _WS_N)
+        assert got == _WS_BYTES[name], name
+        s.close()

@@ -2,7 +2,7 @@
 chain block printed after the call (torch buffers; the null stream and a torch stream; workspace
 prefilled with 0x5A or zeroed).  Test infrastructure: compares with the oracle.
 
-    BLT_LIB_PATH=... python tools/diag_r06.py [--case chained_text] [--cs 4099]
+    BLT_LIB_PATH=... python tools/history/diag_r06.py [--case chained_text] [--cs 4099]
 """
 import argparse
 import os
@@ -10,7 +10,7 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 
 def main():

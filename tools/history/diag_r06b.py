@@ -3,7 +3,7 @@ device API (sync and async, 0x5A workspace) under each blt_debug_set_u16_chain m
 chunk maps, bit 1: the host's extended scan bound).  Prints per mode the mismatching runs, the first
 mismatching token and the pass counts.  Test infrastructure: compares with the oracle.
 
-    python tools/diag_r06b.py [--cs 69633] [--reps 6] [--modes 3,1,2,0]
+    python tools/history/diag_r06b.py [--cs 69633] [--reps 6] [--modes 3,1,2,0]
 """
 import argparse
 import os
@@ -11,7 +11,7 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 
 def main():

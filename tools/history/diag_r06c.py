@@ -3,7 +3,7 @@ on a cyclic map at an odd chunk size, repeated, against a two-pass restatement o
 greedy pass (tokenizer.rs:56-93) per chunk.  Prints each mismatch's position, chunk and the
 neighbourhood.  Test infrastructure only.
 
-    python tools/diag_r06c.py [--cs 69633] [--reps 20]
+    python tools/history/diag_r06c.py [--cs 69633] [--reps 20]
 """
 import argparse
 import os
@@ -11,7 +11,7 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 
 def greedy(m, toks):
