@@ -2275,8 +2275,10 @@ __device__ __forceinline__ void emit_tok(const PassParams& p, uint64_t wtok, uin
         }
     }
     const uint32_t wcnt = uni(lane_u32(lane_off + __popc(L), 63));
-    // in place: output = input when nothing merged before this range or in it
-    if (inplace && wcnt == (rem < kWavePos ? rem : kWavePos) && O + goff == wtok) return;
+    // in place: output = input when nothing merged before this range or in it.  (The counts alone do
+    // not tell: a merge of the range's last token with the next range's first leaves the range all
+    // its tokens, the last one changed.)
+    if (inplace && wcnt == (rem < kWavePos ? rem : kWavePos) && O + goff == wtok && __ballot(M != 0u) == 0) return;
     // one part: the stage holds the range's at most 1024 tokens
     const uint32_t x0 = wave * (uint32_t)kStageTok;   // the wave's stage, logical bytes
     stage_b16_pad(st.v[j], L, stg, x0 + (gb & 15u) + 2u * lane_off);

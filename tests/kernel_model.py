@@ -4,6 +4,10 @@ It reproduces the kernel's decomposition — 16-position lane segments, wave bal
 prefix scans, per-(sub-tile, wave) group functions, the tile function, and the look-back
 composition (done serially here) — so the algebra of the parallel scan can be checked against
 the sequential oracle on CPU, without a GPU.
+
+Below it, the byte pass's chunk geometry (tile_info) restated with the kernel's 32- and 64-bit
+wrap-around arithmetic, for operands far past any input a GPU test can hold
+(tests/test_gpu_byte_modes.py).
 """
 from typing import Dict, Tuple
 
@@ -116,3 +120,74 @@ def run_pass(seq, merges: Dict[Tuple[int, int], int], chunk_size: int):
         O += tile_cnt
         C = co
     return out[:O]
+
+
+# ---- the byte pass's chunk geometry (tile_info, bpe_kernels.hip) ---------------------------------
+# Both branches restated with the kernel's word sizes: the 32-bit one in sub-tile units (chunk sizes
+# that are whole 16 KiB sub-tiles) and the 64-bit one in bytes, each a high multiply with the host's
+# reciprocal and at most two corrections.  Each returns (bge, k0, corrections): the first chunk start
+# at or after the tile start, relative to it and clamped to two tiles; its chunk index; and how many
+# of the two corrections ran.
+SUB_BYTES = 16384          # kSubPosBytes
+M32, M64 = (1 << 32) - 1, (1 << 64) - 1
+SUBS_CAP = (1 << 31) - 8   # run_byte_pass: the 32-bit branch only while n / SUB_BYTES is below this
+
+
+def byte_pass_geometry(n, cs):
+    """(cs_subs, cs_subs_magic, cs_magic) as run_byte_pass (blt_host.cpp) fills them in."""
+    cs_magic = M64 // cs
+    cs_subs = cs_subs_magic = 0
+    if cs % SUB_BYTES == 0 and n // SUB_BYTES < SUBS_CAP:
+        cs_subs = min(cs // SUB_BYTES, 0x7FFFFFFF)
+        cs_subs_magic = M32 // cs_subs if cs_subs > 1 else 0
+    return cs_subs, cs_subs_magic, cs_magic
+
+
+def max_first_subtile(ns):
+    """The largest first sub-tile index NS T of a tile the 32-bit branch meets: the last tile of the
+    longest buffer run_byte_pass admits to it (n / SUB_BYTES = SUBS_CAP - 1)."""
+    n = (SUBS_CAP - 1) * SUB_BYTES + SUB_BYTES - 1
+    ntiles = (n + ns * SUB_BYTES - 1) // (ns * SUB_BYTES)
+    return ns * (ntiles - 1)
+
+
+def tile_info_subs(S, ns, cs_subs, cs_subs_magic):
+    """The 32-bit branch for a tile whose first sub-tile is S (the kernel: S = NS T), uint32 wrap-around."""
+    d = cs_subs
+    S &= M32
+    q = S if d == 1 else (S * cs_subs_magic) >> 32   # __umulhi
+    r = (S - q * d) & M32
+    fixes = 0
+    for _ in range(2):
+        if r >= d:
+            q = (q + 1) & M32
+            r = (r - d) & M32
+            fixes += 1
+    left_subs = (d - r) & M32 if r else 0
+    far = 2 * ns * SUB_BYTES
+    bge = far if left_subs > 2 * ns else (left_subs * SUB_BYTES) & M32
+    return bge, q + (1 if r else 0), fixes
+
+
+def tile_info_bytes(T, ns, cs, cs_magic):
+    """The 64-bit branch for tile T, uint64 wrap-around."""
+    tile0 = (T * ns * SUB_BYTES) & M64
+    q = (tile0 * cs_magic) >> 64   # __umul64hi
+    r = (tile0 - q * cs) & M64
+    fixes = 0
+    for _ in range(2):
+        if r >= cs:
+            q = (q + 1) & M64
+            r = (r - cs) & M64
+            fixes += 1
+    d = (cs - r) & M64 if r else 0
+    far = 2 * ns * SUB_BYTES
+    return min(d, far), (q + (1 if r else 0)) & M64, fixes
+
+
+def tile_info(T, ns, n, cs):
+    """tile_info<NS>(p, T) with the parameters run_byte_pass passes for a buffer of n bytes."""
+    cs_subs, cs_subs_magic, cs_magic = byte_pass_geometry(n, cs)
+    if cs_subs:
+        return tile_info_subs(ns * T, ns, cs_subs, cs_subs_magic)
+    return tile_info_bytes(T, ns, cs, cs_magic)

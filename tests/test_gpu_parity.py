@@ -750,6 +750,30 @@ def test_token_scan_in_place_prefix(where):
         assert np.array_equal(lens, elens)
 
 
+@pytest.mark.parametrize("r", [1, 16, 32, 37])
+def test_token_scan_in_place_lone_merge_at_range_end(r):
+    """The second pass's only merge joins the last token of wave range r - 1 with the first of range
+    r (a wave range, sub-tile or tile edge): range r - 1 keeps all its 1024 tokens and nothing merged
+    before it, yet its last token changes, so the in-place pass must write it.  On the two-kernel
+    chain (the in-place scan pass) and with the fused first two passes."""
+    n = 4 * TOK_TILE                                          # pass 1: "xy" -> 256 everywhere, 2 tiles of tokens
+    data = np.frombuffer(b"xy" * (n // 2), np.uint8).copy()
+    k = 2048 * r - 2                                          # "ab" -> 257 at tokens 1024 r - 1 and 1024 r
+    data[k:k + 4] = np.frombuffer(b"abab", np.uint8)
+    m = {(120, 121): 256, (97, 98): 257, (257, 257): 258}
+    s = blt_amd.BpeStrategy(m)
+    exp = O.COracle(m).run(data, n, threads=4)
+    L = blt_amd._lib.lib()
+    for fused in (0, 1):
+        L.blt_debug_set_fused(fused)
+        try:
+            got = s.process_chunks(data, n)
+        finally:
+            L.blt_debug_set_fused(1)
+        assert L.blt_debug_last_fused() == fused
+        assert np.array_equal(got, exp), fused
+
+
 def test_token_scan_device_api_in_place():
     """encode_device on a general map: the u16 passes work in the caller's output buffer; the
     chunk offsets and the token count match the oracle, and repeated async calls agree."""
